@@ -7,7 +7,14 @@ t % world == rank (yk_render_shard), the film sums are reduced to rank 0 over
 RCCL (torch.distributed "nccl") and rank 0 normalises the frame
 (yk_film_resolve). Total work is fixed as N grows ("scaling": "strong").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+its roofline entry is computed from the timed frames' own HIP events.
+--dump-outputs DIR also writes what the last timed step returned (rank 0's
+resolved frame and film sums) as DIR/<name>.npy. --full adds the measurements
+that take runs of their own: the serialised roofline frame and the CPU
+baseline (--no-roofline-frame / --no-cpu leave one of them out again).
 
 Under torch.distributed.run every process is one rank. Started directly with
 --gpus N > 1, bench.py starts the N rank processes itself (launch_ranks)
@@ -62,8 +69,16 @@ def main():
                          "(the photon maps are built once before timing, like the kd-tree)")
     ap.add_argument("--photons", type=int, default=100000, help="photon: diffuse photons (reference default)")
     ap.add_argument("--fg-samples", type=int, default=32, help="photon: final-gather paths per hit (default 32)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target length of the CPU baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the serialised roofline frame and the CPU baseline "
+                         "(off by default: a plain run measures the headline figure only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float32: "
+                         "rgba (the resolved frame) and film (the film sums), each in full or, above its share "
+                         "of 64 MB, as a fixed seeded sample")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="--full: target length of the CPU baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: leave the CPU baseline out")
     ap.add_argument("--gpu-tree", action="store_true",
                     help="replace the reference kd-tree by the device-built binned-SAH tree (yk_device_build_tree, "
                          "documented tie-break; not the parity default)")
@@ -74,11 +89,13 @@ def main():
     ap.add_argument("--pipes", type=int, default=0,
                     help="batch pipelines of the timed frames (default: libyk's 4; 1 serialises the kernels)")
     ap.add_argument("--no-roofline-frame", action="store_true",
-                    help="skip the extra serialised frame the roofline line is measured on")
+                    help="--full: skip the extra serialised frame the roofline line is measured on")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="film-reduce backend for N > 1: nccl (RCCL over xGMI, one GPU per rank) or gloo (host "
                          "copies; lets N ranks share one GPU, for tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.pipes:
         os.environ["YK_PIPES"] = str(args.pipes)
 
@@ -164,10 +181,13 @@ def main():
     st = A.yk_stats()
     barrier()
     t0 = time.perf_counter()
+    rgba = None
     for _ in range(args.steps):
-        step(st, red_ev)
+        rgba = step(st, red_ev)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before any further frame overwrites the film
+        dump_outputs(args.dump_outputs, {"rgba": (rgba, DUMP_RGBA_ELEMS), "film": (film, DUMP_FILM_ELEMS)})
     # RCCL film reduce per step (inside the timed region; 0 on one GPU)
     ms_reduce = sum(a.elapsed_time(b) for a, b in red_ev) / max(args.steps, 1)
 
@@ -189,13 +209,13 @@ def main():
     rays = w[0] + w[1]
     value = rays / elapsed / 1e6
 
-    # Roofline frame: one more frame (not part of `value`) with the kernels
+    # Roofline frame (--full): one more frame (not part of `value`) with the kernels
     # serialised on one pipeline (YK_PIPES=1), so that each traversal
     # launch's HIP-event duration is its own and not time shared with the
     # other pipes' kernels. rocprofv3 --kernel-trace --stats of
     # `bench.py --pipes 1` gives the same per-launch averages (profiles/).
     rst = None
-    if not args.no_roofline_frame:
+    if args.full and not args.no_roofline_frame:
         prev = os.environ.get("YK_PIPES")
         os.environ["YK_PIPES"] = "1"
         rst = A.yk_stats()
@@ -214,7 +234,7 @@ def main():
     roofline = roofline_line(args, w, ms_c, ms_s, rst, elapsed, pm_info is None, small, shadow_split(dev, p))
 
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         cpu = cpu_baseline(scene, p, args.cpu_seconds)
 
     out = {
@@ -263,6 +283,24 @@ def main():
     print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_RGBA_ELEMS = 10_000_000  # 40 MB of float32: the 1920x1080 frame (8.3M values) in full
+DUMP_FILM_ELEMS = 5_000_000   # 20 MB: with the frame, under the 64 MB a dump may take
+DUMP_SEED = 20240613
+
+
+def dump_outputs(outdir, arrays):
+    """Writes {name: (cuda tensor, max elements)} as outdir/name.npy (float32).
+    A tensor above its limit is written as a 1-D sample at flat indices drawn
+    once from a fixed seed (the same indices for the same shape in every run
+    and build), so that two dumps compare value for value."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, (t, limit) in arrays.items():
+        if t.numel() > limit:
+            idx = np.random.default_rng(DUMP_SEED).integers(0, t.numel(), limit)
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
 
 
 def _hook(fn, *args):

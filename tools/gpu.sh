@@ -58,16 +58,16 @@ for s in "$@"; do
     timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1
     tail -1 $O/smoke.txt ;;
   bench)
-    timeout -k 10 400 python -u bench.py > $O/bench.json 2> $O/bench.err
+    timeout -k 10 400 python -u bench.py --full > $O/bench.json 2> $O/bench.err
     head -c 400 $O/bench.json; echo ;;
   c2)
-    timeout -k 10 300 python -u bench.py $C2 > $O/bench_c2.json 2> $O/bench_c2.err
+    timeout -k 10 300 python -u bench.py --full $C2 > $O/bench_c2.json 2> $O/bench_c2.err
     head -c 300 $O/bench_c2.json; echo ;;
   pm)
-    timeout -k 10 400 python -u bench.py $PM > $O/bench_pm.json 2> $O/bench_pm.err
+    timeout -k 10 400 python -u bench.py --full $PM > $O/bench_pm.json 2> $O/bench_pm.err
     head -c 300 $O/bench_pm.json; echo ;;
   hair)
-    timeout -k 10 500 python -u bench.py $HAIR --no-cpu > $O/bench_hair.json 2> $O/bench_hair.err
+    timeout -k 10 500 python -u bench.py --full $HAIR --no-cpu > $O/bench_hair.json 2> $O/bench_hair.err
     head -c 300 $O/bench_hair.json; echo ;;
   prof|prof_c2|prof_hair|prof_pm)
     A=""; [ $s = prof_c2 ] && A="$C2"; [ $s = prof_hair ] && A="$HAIR"; [ $s = prof_pm ] && A="$PM"
