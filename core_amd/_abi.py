@@ -15,7 +15,7 @@ YK_OK = 0
 YK_ERR_ABORTED = 7
 YK_ERR_ARG, YK_ERR_STATE, YK_ERR_HIP, YK_ERR_UNSUPPORTED, YK_ERR_ALLOC, YK_ERR_INTERNAL = 1, 2, 3, 4, 5, 6
 YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT = 0, 1
-YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL = 0, 1, 2
+YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_MESH_SMOOTH, YK_MESH_NORMALS_EXPORTED = 1, 2
 YK_INTEGRATOR_DIRECT, YK_INTEGRATOR_PATH, YK_INTEGRATOR_PHOTON = 0, 1, 2
 YK_PHOTON_MAP_DIFFUSE, YK_PHOTON_MAP_CAUSTIC, YK_PHOTON_MAP_RADIANCE = 0, 1, 2
@@ -44,7 +44,9 @@ class yk_material(C.Structure):
 class yk_light(C.Structure):
     _fields_ = [("type", C.c_int32), ("corner", f3), ("point1", f3), ("point2", f3),
                 ("color", f3), ("power", C.c_float), ("samples", C.c_int32),
-                ("from_", f3), ("direction", f3), ("radius", C.c_float), ("infinite", C.c_int32)]
+                ("from_", f3), ("direction", f3), ("radius", C.c_float), ("infinite", C.c_int32),
+                ("to", f3), ("cone_angle", C.c_float), ("blend", C.c_float), ("soft_shadows", C.c_int32),
+                ("shadow_fuzzyness", C.c_float), ("photon_only", C.c_int32)]
 
 
 class yk_camera(C.Structure):
@@ -70,6 +72,18 @@ class yk_area_light_state(C.Structure):
 class yk_dirac_light_state(C.Structure):
     _fields_ = [("type", C.c_int32), ("position", f3), ("direction", f3), ("color", f3),
                 ("radius", C.c_float), ("infinite", C.c_int32)]
+
+
+class yk_spot_light_state(C.Structure):
+    _fields_ = [("position", f3), ("dir", f3), ("ndir", f3), ("du", f3), ("dv", f3),
+                ("cos_start", C.c_float), ("cos_end", C.c_float), ("icos_diff", C.c_float), ("color", f3),
+                ("soft_shadows", C.c_int32), ("shadow_fuzzyness", C.c_float), ("samples", C.c_int32),
+                ("photon_only", C.c_int32)]
+
+
+class yk_sphere_light_state(C.Structure):
+    _fields_ = [("center", f3), ("radius", C.c_float), ("square_radius", C.c_float),
+                ("square_radius_epsilon", C.c_float), ("area", C.c_float), ("color", f3), ("samples", C.c_int32)]
 
 
 class yk_camera_state(C.Structure):
@@ -183,6 +197,10 @@ SIGNATURES = {
     "yk_scene_get_area_light_state": (C.c_int, [P, i32, C.POINTER(yk_area_light_state)]),
     "yk_scene_add_dirac_light_state": (C.c_int, [P, C.POINTER(yk_dirac_light_state)]),
     "yk_scene_get_dirac_light_state": (C.c_int, [P, i32, C.POINTER(yk_dirac_light_state)]),
+    "yk_scene_add_spot_light_state": (C.c_int, [P, C.POINTER(yk_spot_light_state)]),
+    "yk_scene_get_spot_light_state": (C.c_int, [P, i32, C.POINTER(yk_spot_light_state)]),
+    "yk_scene_add_sphere_light_state": (C.c_int, [P, C.POINTER(yk_sphere_light_state)]),
+    "yk_scene_get_sphere_light_state": (C.c_int, [P, i32, C.POINTER(yk_sphere_light_state)]),
     "yk_scene_set_background": (C.c_int, [P, fp, C.c_float]),
     "yk_scene_get_background": (C.c_int, [P, fp, i32p]),
     "yk_scene_get_camera_state": (C.c_int, [P, C.POINTER(yk_camera_state)]),

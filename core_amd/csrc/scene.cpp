@@ -128,6 +128,80 @@ yk_dirac_light_state dirac_state(const yk_light& l) {
   return o;
 }
 
+// createCS (vector3d.h:316-334): d = 1.0 / fSqrt(..) is a double division of
+// float values rounded to float, which equals the float division
+static void create_cs(const float* N, float* u, float* v) {
+  if (N[0] == 0.f && N[1] == 0.f) {
+    u[0] = N[2] < 0.f ? -1.f : 1.f;
+    u[1] = 0.f;
+    u[2] = 0.f;
+    v[0] = 0.f;
+    v[1] = 1.f;
+    v[2] = 0.f;
+    return;
+  }
+  const float d = (float)(1.0 / (double)std::sqrt(N[1] * N[1] + N[0] * N[0]));
+  u[0] = N[1] * d;
+  u[1] = -N[0] * d;
+  u[2] = 0.f;
+  v[0] = N[1] * u[2] - N[2] * u[1];
+  v[1] = N[2] * u[0] - N[0] * u[2];
+  v[2] = N[0] * u[1] - N[1] * u[0];
+}
+
+// spotLight_t::spotLight_t, spotlight.cc:63-75: ndir = (from - to).normalize(),
+// the angles in double (degToRad), fCos on their float values, icosDiff in double
+yk_spot_light_state spot_state(const yk_light& l) {
+  yk_spot_light_state o{};
+  float nd[3] = {l.from[0] - l.to[0], l.from[1] - l.to[1], l.from[2] - l.to[2]};
+  float len = nd[0] * nd[0] + nd[1] * nd[1] + nd[2] * nd[2];  // vector3d_t::normalize, vector3d.h:249-260
+  if (len != 0.f) {
+    len = 1.0f / std::sqrt(len);
+    for (float& x : nd) x *= len;
+  }
+  for (int k = 0; k < 3; ++k) {
+    o.position[k] = l.from[k];
+    o.ndir[k] = nd[k];
+    o.dir[k] = -nd[k];
+    o.color[k] = l.color[k] * l.power;
+  }
+  create_cs(o.dir, o.du, o.dv);
+  const double rad_angle = (double)l.cone_angle * 0.01745329251994329576922;  // degToRad
+  const double rad_inner_angle = rad_angle * (double)(1.f - l.blend);
+  o.cos_start = host_fcos((float)rad_inner_angle);
+  o.cos_end = host_fcos((float)rad_angle);
+  o.icos_diff = (float)(1.0 / (double)(o.cos_start - o.cos_end));
+  o.soft_shadows = l.soft_shadows ? 1 : 0;
+  o.shadow_fuzzyness = l.shadow_fuzzyness;
+  o.samples = l.samples;
+  o.photon_only = l.photon_only ? 1 : 0;
+  return o;
+}
+
+// sphereLight_t::sphereLight_t, spherelight.cc:64-72
+yk_sphere_light_state sphere_state(const yk_light& l) {
+  yk_sphere_light_state o{};
+  for (int k = 0; k < 3; ++k) {
+    o.center[k] = l.from[k];
+    o.color[k] = l.color[k] * l.power;
+  }
+  o.radius = l.radius;
+  o.square_radius = l.radius * l.radius;
+  o.square_radius_epsilon = (float)((double)o.square_radius * 1.000003815);
+  o.area = (float)((double)o.square_radius * 4.0 * 3.14159265358979323846);
+  o.samples = l.samples;
+  return o;
+}
+
+int light_slots(const Scene& s, size_t i) {
+  switch (s.light_kind[i]) {
+    case YK_LIGHT_AREA: return 2 * s.light_states[i].samples;  // light samples + BSDF (MIS) samples
+    case YK_LIGHT_SPOT: return s.spot_states[i].soft_shadows ? 2 * s.spot_states[i].samples : 1;
+    case YK_LIGHT_SPHERE: return s.sphere_states[i].samples;  // canIntersect() is false: no MIS half
+    default: return 1;
+  }
+}
+
 yk_camera_state camera_state(const yk_camera& c) {  // camera_t ctor + setAxis
   yk_camera_state o{};
   const hv3 pos = H(c.from), look = H(c.to), up = H(c.up);
@@ -188,15 +262,13 @@ void Scene::add_light(const yk_light& l) {
   lights.push_back(l);
   light_has_params.push_back(true);
   light_kind.push_back(l.type);
-  if (l.type == YK_LIGHT_AREA) {
-    light_states.push_back(light_state(l));
-    dirac_states.push_back(yk_dirac_light_state{});
-  } else {
-    yk_area_light_state a{};
-    a.samples = 1;
-    light_states.push_back(a);
-    dirac_states.push_back(dirac_state(l));
-  }
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(l.type == YK_LIGHT_AREA ? light_state(l) : a);
+  dirac_states.push_back(l.type == YK_LIGHT_POINT || l.type == YK_LIGHT_DIRECTIONAL ? dirac_state(l)
+                                                                                  : yk_dirac_light_state{});
+  spot_states.push_back(l.type == YK_LIGHT_SPOT ? spot_state(l) : yk_spot_light_state{});
+  sphere_states.push_back(l.type == YK_LIGHT_SPHERE ? sphere_state(l) : yk_sphere_light_state{});
 }
 void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   lights.push_back(yk_light{});
@@ -206,6 +278,8 @@ void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   a.samples = 1;
   light_states.push_back(a);
   dirac_states.push_back(l);
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(yk_sphere_light_state{});
 }
 void Scene::add_light_state(const yk_area_light_state& l) {
   lights.push_back(yk_light{});
@@ -213,6 +287,30 @@ void Scene::add_light_state(const yk_area_light_state& l) {
   light_kind.push_back(YK_LIGHT_AREA);
   light_states.push_back(l);
   dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(yk_sphere_light_state{});
+}
+void Scene::add_spot_light_state(const yk_spot_light_state& l) {
+  lights.push_back(yk_light{});
+  light_has_params.push_back(false);
+  light_kind.push_back(YK_LIGHT_SPOT);
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(a);
+  dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(l);
+  sphere_states.push_back(yk_sphere_light_state{});
+}
+void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
+  lights.push_back(yk_light{});
+  light_has_params.push_back(false);
+  light_kind.push_back(YK_LIGHT_SPHERE);
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(a);
+  dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(l);
 }
 void Scene::set_camera(const yk_camera& c) {
   camera = c;

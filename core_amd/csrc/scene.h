@@ -49,6 +49,8 @@ struct Scene {
   std::vector<int> light_kind;                      // YK_LIGHT_*, scene light order
   std::vector<yk_area_light_state> light_states;    // area lights (zero entry for Dirac lights)
   std::vector<yk_dirac_light_state> dirac_states;   // point / directional (zero entry for area lights)
+  std::vector<yk_spot_light_state> spot_states;     // spot lights (zero entry for every other kind)
+  std::vector<yk_sphere_light_state> sphere_states; // sphere lights (zero entry for every other kind)
   bool has_background = false;
   float background[3] = {0.f, 0.f, 0.f};            // constBackground_t::color (color*power)
   yk_camera_state camera_state{};
@@ -59,6 +61,8 @@ struct Scene {
   void add_light(const yk_light& l);
   void add_light_state(const yk_area_light_state& l);
   void add_dirac_light_state(const yk_dirac_light_state& l);
+  void add_spot_light_state(const yk_spot_light_state& l);
+  void add_sphere_light_state(const yk_sphere_light_state& l);
   void set_camera(const yk_camera& c);
   void set_camera_state(const yk_camera_state& c);
 
@@ -89,6 +93,11 @@ void gen_bumpy(Scene& s, int nu, int nv, int resx, int resy);
 yk_material_state material_state(const yk_material& m);
 yk_area_light_state light_state(const yk_light& l);
 yk_dirac_light_state dirac_state(const yk_light& l);
+// spotLight_t ctor (spotlight.cc:63-75), sphereLight_t ctor (spherelight.cc:64-72)
+yk_spot_light_state spot_state(const yk_light& l);
+yk_sphere_light_state sphere_state(const yk_light& l);
+// shadow slots of one doLightEstimation of scene light i (DLight.nslots)
+int light_slots(const Scene& s, size_t i);
 yk_camera_state camera_state(const yk_camera& c);
 
 // recNormal: ((b-a)^(c-a)).normalize() with the reference's float op order

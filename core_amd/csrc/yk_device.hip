@@ -31,6 +31,7 @@
 
 #include "../../include/yk_api.h"
 #include "../../include/yk_test_hooks.h"
+#include "../../include/yk_test_hooks_light.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"
@@ -80,6 +81,13 @@ struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-4
   // directionalLight_t after init(scene) (directional.cc:52-75): photon disk
   // centre / radius (infinite: scene-bound centre and world radius), createCS frame
   float epos[3], edu[3], edv[3], eradius, wradius;
+  // spotLight_t members (spotlight.cc:46-60): pos = position, dir, du / dv =
+  // createCS(dir) (the area light's fields, unused by a spot), and
+  float ndir[3], cos_start, cos_end, icos_diff, fuzzy;
+  int soft;         // softShadows: illumSample + intersect instead of illuminate
+  int photon_only;  // illuminate / illumSample return false
+  // sphereLight_t members (spherelight.cc:56-61): pos = center, radius, area, and
+  float sq_radius, sq_radius_eps;
 };
 
 struct DCam {  // perspectiveCam_t after camera_t ctor + setAxis
@@ -1083,7 +1091,8 @@ size_t small_scene_bytes(size_t nn, size_t ntris, size_t nlref) {
 // the positive quiet NaN, never as the sentinel
 constexpr unsigned kTmaxInf = 0xFFC00000u;  // negative quiet NaN
 __device__ __forceinline__ float shadow_w(float tmax) {
-  return tmax < 0.f ? __uint_as_float(kTmaxInf) : (tmax != tmax ? __uint_as_float(0x7FC00000u) : tmax);
+  // fabsf: a tmax of -0 loses its sign bit, which marks a MIS ray (unpack_shadow)
+  return tmax < 0.f ? __uint_as_float(kTmaxInf) : (tmax != tmax ? __uint_as_float(0x7FC00000u) : fabsf(tmax));
 }
 // the shadow ray of slot record dw and origin record o (inverse of the
 // encodings above; every value read back is the one the shading computed)
@@ -1095,7 +1104,7 @@ __device__ __forceinline__ yk_ray unpack_shadow(float4 dw, float4 o) {
   r.dir[0] = dw.x;
   r.dir[1] = dw.y;
   r.dir[2] = dw.z;
-  const bool inf = __float_as_uint(dw.w) == kTmaxInf, mis = !inf && dw.w < 0.f;
+  const bool inf = __float_as_uint(dw.w) == kTmaxInf, mis = !inf && (__float_as_uint(dw.w) >> 31) != 0u;
   r.tmin = mis ? YK_MIN_RAYDIST : o.w;
   r.tmax = inf ? -1.f : (mis ? -dw.w : dw.w);
   return r;
@@ -1960,18 +1969,147 @@ __device__ __forceinline__ bool light_hit(const DLight& L, v3 from, v3 dir, floa
   return true;
 }
 
+// sampleCone, sample_utils.h:76-82: float throughout, t1 = M_2PI * s1 in double
+__device__ __forceinline__ v3 sample_cone(v3 D, v3 U, v3 V, float maxCosAng, float s1, float s2) {
+  const float cosAng = 1.f - (1.f - maxCosAng) * s2;
+  const float sinAng = sqrtf(1.f - cosAng * cosAng);
+  const float t1 = (float)(YK_2PI_D * (double)s1);
+  const float ct = fcos_ref(t1), st = fsin_ref(t1);
+  return V3((U.x * ct + V.x * st) * sinAng + D.x * cosAng, (U.y * ct + V.y * st) * sinAng + D.y * cosAng,
+            (U.z * ct + V.z * st) * sinAng + D.z * cosAng);
+}
+
+// The spot cone's falloff at cosa (spotlight.cc:127-136 and its copies in
+// illumSample / intersect): false outside the outer cone; v = 1 inside the
+// inner cone, where the reference takes `color` as is (color * 1 has its
+// bits), else the smoothstep of (cosa - cosEnd) * icosDiff.
+__device__ __forceinline__ bool spot_falloff(const DLight& L, float cosa, float& v) {
+  if (cosa < L.cos_end) return false;
+  v = 1.f;
+  if (!(cosa >= L.cos_start)) {
+    const float x = (cosa - L.cos_end) * L.icos_diff;
+    v = (x * x) * (3.f - 2.f * x);
+  }
+  return true;
+}
+
+// spotLight_t::illumSample, spotlight.cc:144-175; ls.col = color * cv
+__device__ __forceinline__ bool spot_illum(const DLight& L, v3 P, float s1, float s2, v3& ldir, float& tmax,
+                                           float& pdf, float& cv) {
+  if (L.photon_only) return false;
+  const v3 l = vsub(ld3(L.pos), P);
+  const float dist_sqr = l.x * l.x + l.y * l.y + l.z * l.z;
+  if (dist_sqr == 0.f) return false;
+  const float dist = sqrtf(dist_sqr);
+  const float inv = 1.f / dist;
+  const v3 ld = V3(l.x * inv, l.y * inv, l.z * inv);
+  if (!spot_falloff(L, vdot(ld3(L.ndir), ld), cv)) return false;
+  tmax = dist;
+  ldir = sample_cone(ld, ld3(L.du), ld3(L.dv), L.cos_end, s1 * L.fuzzy, s2 * L.fuzzy);
+  pdf = dist_sqr;
+  return true;
+}
+
+// spotLight_t::intersect, spotlight.cc:243-280, restated as written, with its
+// two quirks: the hit point must lie on the plane through `position` exactly
+// (== 0 in float, which almost no ray meets), and `P*P <= 1e-2` measures the
+// hit point's distance from the world origin, not from the light. The log
+// line is left out. col = color * cv.
+__device__ __forceinline__ bool spot_hit(const DLight& L, v3 from, v3 dir, float& t, float& ipdf, float& cv) {
+  const v3 d = ld3(L.dir);
+  const float cosA = vdot(d, dir);
+  if (cosA == 0.f) return false;
+  t = vdot(d, vsub(ld3(L.pos), from)) / cosA;
+  if (t < 0.f) return false;
+  const v3 P = V3(from.x + t * dir.x, from.y + t * dir.y, from.z + t * dir.z);
+  if (!(vdot(d, vsub(P, ld3(L.pos))) == 0.f)) return false;
+  if (!((double)vdot(P, P) <= 1e-2)) return false;
+  if (!spot_falloff(L, cosA, cv)) return false;
+  ipdf = 1.f / (t * t);
+  return true;
+}
+
+// sphereIntersect, spherelight.cc:88-100: float members, the literals 2.0 /
+// 4.0 make osc and the two roots double expressions rounded to float
+__device__ __forceinline__ bool sphere_isect(v3 from, v3 dir, v3 c, float R2, float& d1, float& d2) {
+  const v3 vf = vsub(from, c);
+  const float ea = vdot(dir, dir);
+  const float eb = vdot(vmul(2.0f, vf), dir);
+  const float ec = vdot(vf, vf) - R2;
+  float osc = (float)((double)(eb * eb) - 4.0 * (double)ea * (double)ec);
+  if (osc < 0.f) {  // "assume tangential hit/miss condition => Pythagoras"
+    d1 = sqrtf(ec / ea);
+    return false;
+  }
+  osc = sqrtf(osc);
+  d1 = (float)((double)(-eb - osc) / (2.0 * (double)ea));
+  d2 = (float)((double)(-eb + osc) / (2.0 * (double)ea));
+  return true;
+}
+
+// sphereLight_t::illumSample, spherelight.cc:102-132: the cone under which
+// the sphere is seen from P, sampled around a per-point createCS frame
+__device__ __forceinline__ bool sphere_illum(const DLight& L, v3 P, float s1, float s2, v3& ldir, float& tmax,
+                                             float& pdf) {
+  v3 cdir = vsub(ld3(L.pos), P);
+  const float dist_sqr = cdir.x * cdir.x + cdir.y * cdir.y + cdir.z * cdir.z;
+  if (dist_sqr <= L.sq_radius) return false;  // only emits on the outside
+  const float dist = sqrtf(dist_sqr);
+  const float idist_sqr = 1.f / dist_sqr;
+  const float cosAlpha = sqrtf(1.f - L.sq_radius * idist_sqr);
+  const float inv = 1.f / dist;
+  cdir = V3(cdir.x * inv, cdir.y * inv, cdir.z * inv);
+  v3 du, dv;
+  create_cs(cdir, du, dv);
+  const v3 dir = sample_cone(cdir, du, dv, cosAlpha, s1, s2);
+  float d1, d2;
+  if (!sphere_isect(P, dir, ld3(L.pos), L.sq_radius_eps, d1, d2)) return false;
+  ldir = dir;
+  tmax = d1;
+  pdf = 1.f / (2.f * (1.f - cosAlpha));
+  return true;
+}
+
+// sphereLight_t::intersect, spherelight.cc:134-149. It never writes t: a ray
+// tested with it would keep ray_t's default tmax (-1, unbounded; ray.h:29).
+// doLightEstimation does not call it, because sphereLight_t::canIntersect()
+// is false (spherelight.cc:49; mcintegrator.cc:109,134,156): a sphere light
+// gets no BSDF (MIS) half and no MIS weight. Only yk_debug_light_probe runs it.
+__device__ __forceinline__ bool sphere_hit(const DLight& L, v3 from, v3 dir, float& ipdf) {
+  float d1, d2;
+  if (!sphere_isect(from, dir, ld3(L.pos), L.sq_radius, d1, d2)) return false;
+  const v3 cdir = vsub(ld3(L.pos), from);
+  const float dist_sqr = cdir.x * cdir.x + cdir.y * cdir.y + cdir.z * cdir.z;
+  if (dist_sqr <= L.sq_radius) return false;
+  const float idist_sqr = 1.f / dist_sqr;
+  const float cosAlpha = sqrtf(1.f - L.sq_radius * idist_sqr);
+  ipdf = 2.f * (1.f - cosAlpha);
+  return true;
+}
+
 // pointLight_t::illuminate (pointlight.cc:60-75) / directionalLight_t::
 // illuminate (directional.cc:77-96), compiled forms: |v|^2 as (x*x + y*y) + z*z,
 // 1/dist and 1/dist^2 as separate divisions; col = color * (1/dist^2).
+// A hard spot (spotLight_t::illuminate, spotlight.cc:113-142) runs the point
+// light's arithmetic and scales 1/dist^2 by the cone's falloff, which is
+// exactly 1 inside the inner cone: there its results are the point light's bits.
+template <bool XL = true>
 __device__ __forceinline__ bool dirac_illum(const DLight& L, v3 P, v3& ldir, float& tmax, c3& col) {
-  if (L.type == YK_LIGHT_POINT) {
+  if (L.type == YK_LIGHT_POINT || (XL && L.type == YK_LIGHT_SPOT)) {
+    if (XL && L.type == YK_LIGHT_SPOT && L.photon_only) return false;
     const v3 l = vsub(ld3(L.pos), P);
     const float dist_sqr = l.x * l.x + l.y * l.y + l.z * l.z;
     const float dist = sqrtf(dist_sqr);
     if (dist == 0.f) return false;
-    const float idist_sqr = 1.f / dist_sqr;
+    float idist_sqr = 1.f / dist_sqr;
     const float inv = 1.f / dist;
-    ldir = V3(l.x * inv, l.y * inv, l.z * inv);
+    const v3 ld = V3(l.x * inv, l.y * inv, l.z * inv);
+    if (XL && L.type == YK_LIGHT_SPOT) {
+      float v;
+      if (!spot_falloff(L, vdot(ld3(L.ndir), ld), v)) return false;
+      idist_sqr = v * idist_sqr;  // color * (v * idist_sqr); v = 1 keeps idist_sqr's bits
+    }
+    ldir = ld;
     tmax = dist;
     col = C3(L.color[0] * idist_sqr, L.color[1] * idist_sqr, L.color[2] * idist_sqr);
     return true;
@@ -2412,7 +2550,8 @@ template <bool MIS>
 __device__ __forceinline__ int emit_shadow(const Batch& B, long long slot, v3 P, v3 dir, float tmax, int kbit,
                                            unsigned long long& traced) {
   if (B.split) {
-    st_f4(&B.s_dir[slot], dir.x, dir.y, dir.z, MIS ? -tmax : shadow_w(tmax));
+    // a soft spot's hit may lie at t = +-0 (spot_hit): the sign bit alone marks a MIS ray
+    st_f4(&B.s_dir[slot], dir.x, dir.y, dir.z, MIS ? -fabsf(tmax) : shadow_w(tmax));
   } else {
     yk_ray sr;
     put_ray(sr, P, dir, MIS ? YK_MIN_RAYDIST : YK_SHADOW_BIAS, tmax);
@@ -2427,23 +2566,42 @@ __device__ __forceinline__ void put_org(const Batch& B, long long c, v3 P) {
   if (B.split) st_f4(&B.s_dir[slot_of(B, c, B.K)], P.x, P.y, P.z, YK_SHADOW_BIAS);
 }
 
-// mcIntegrator_t::doLightEstimation (area light), mcintegrator.cc:73-195, split
+// light_t::diracLight(): point, directional and hard spot lights take
+// doLightEstimation's one-ray branch, the others its sample loops
+__device__ __forceinline__ bool light_sampled(const DLight& L) {
+  return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.soft != 0;
+}
+
+template <bool DIFF, int KIND>
+__device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
+                                           const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
+                                           unsigned loffs, unsigned long long& traced);
+
+// mcIntegrator_t::doLightEstimation, mcintegrator.cc:73-195, split
 // at its isShadowed calls: every shadow ray it would trace is written to its
 // slot with the contribution it adds when unoccluded. Returns #rays; sets bit
 // k of `traced` (k < 64) for each slot that holds a ray.
-template <bool DIFF = false>
+template <bool DIFF = false, bool XL = false>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
                                          unsigned long long& traced, const DMat* mats = c_mats) {
   const DLight& L = c_lights[li];
   const DMat& M = mats[sp.mat];
   const c3 black = C3(0.f, 0.f, 0.f);
-  if (L.type != YK_LIGHT_AREA) {  // Dirac branch, mcintegrator.cc:85-100: one shadow ray
+  // the light's kind is the same for every lane: one scalar branch per light,
+  // outside the sample loops
+  if (L.type == YK_LIGHT_AREA)
+    return gen_sampled<DIFF, YK_LIGHT_AREA>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  if (XL && L.type == YK_LIGHT_SPHERE)
+    return gen_sampled<DIFF, YK_LIGHT_SPHERE>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  if (XL && L.soft)
+    return gen_sampled<DIFF, YK_LIGHT_SPOT>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  {  // Dirac branch, mcintegrator.cc:85-100: one shadow ray
     const long long slot = slot_of(B, c, k0);
     v3 ldir;
     float ltmax;
     c3 lc;
-    if (!dirac_illum(L, sp.P, ldir, ltmax, lc)) {
+    if (!dirac_illum<XL>(L, sp.P, ldir, ltmax, lc)) {
       put_slot(B, slot, 0, black);
       return 0;
     }
@@ -2461,6 +2619,22 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
              C3((lc.r * surf.r) * f, (lc.g * surf.g) * f, surf.b * (lc.b * f)));
     return nq;
   }
+}
+
+// doLightEstimation's branch for lights with illumSample (mcintegrator.cc:
+// 101-193). Three things depend on the light's kind (KIND, a YK_LIGHT_*):
+// its sample function, its intersect function and ls.col / lcol -- the
+// colour as is for area and sphere lights, the colour times the cone's
+// falloff cv for a soft spot (kept in the slot's aux record under
+// transparent shadows, which filter the colour first). A sphere light's
+// canIntersect() is false (spherelight.cc:49): no MIS weight on its light
+// samples and no BSDF half, so it owns `samples` slots, not 2 * samples.
+template <bool DIFF, int KIND>
+__device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
+                                           const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
+                                           unsigned loffs, unsigned long long& traced) {
+  constexpr bool CAN_INTERSECT = KIND != YK_LIGHT_SPHERE;
+  const c3 black = C3(0.f, 0.f, 0.f);
   const int n = L.samples;
   const unsigned offs = (unsigned)(n * (int)pixelSample) + soffs + loffs * 4567u;
   const c3 lcol = C3(L.color[0], L.color[1], L.color[2]);
@@ -2473,8 +2647,12 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
     const float s1 = hal_next(h2), s2 = hal_next(h3);
     const long long slot = slot_of(B, c, k0 + i);
     v3 ldir;
-    float ltmax, lpdf;
-    if (!light_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf)) {
+    float ltmax, lpdf, cv = 1.f;
+    bool lit;
+    if (KIND == YK_LIGHT_AREA) lit = light_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
+    else if (KIND == YK_LIGHT_SPOT) lit = spot_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf, cv);
+    else lit = sphere_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
+    if (!lit) {
       put_slot(B, slot, 0, black);
       continue;
     }
@@ -2484,7 +2662,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
       continue;
     }
     const c3 surf = mat_eval<!DIFF>(M, sp, wo, ldir);
-    const float mPdf = mat_pdf(M, sp, wo, ldir);
+    const float mPdf = CAN_INTERSECT ? mat_pdf(M, sp, wo, ldir) : 0.f;
     // compiled form: ((surf*lcol) * (|N.l| * (1/pdf))) [* w]
     const float k = fabsf(vdot(sp.N, ldir)) * (1.0f / lpdf);
     float w = 1.f;
@@ -2494,15 +2672,16 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
     }
     if (B.ts) {  // ls.col *= scol first (mcintegrator.cc:130)
       put_slot(B, slot, SL_TRACED | SL_ADDS, surf);
-      put_aux(B, slot, k, w, mPdf > 1e-6f ? 1.f : 0.f, 0.f);
+      put_aux(B, slot, k, w, mPdf > 1e-6f ? 1.f : 0.f, KIND == YK_LIGHT_SPOT ? cv : 0.f);
       continue;
     }
-    const c3 sl = cmul(surf, lcol);
+    const c3 sl = cmul(surf, KIND == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol);
     c3 v;
     if (mPdf > 1e-6f) v = C3((sl.r * k) * w, (sl.g * k) * w, (sl.b * k) * w);
     else v = C3(sl.r * k, sl.g * k, sl.b * k);
     put_slot(B, slot, SL_TRACED | SL_ADDS, v);
   }
+  if (!CAN_INTERSECT) return nr;
   h2 = h2_start;
   h3 = h3_start;
   for (int i = 0; i < n; ++i) {
@@ -2514,12 +2693,17 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
     const c3 surf = mat_sample<DIFF>(M, sp, wo, bdir, s1, s2,
                                      BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT, spdf,
                                      W, ok);
-    float bt, lightPdf;
-    if (!(spdf > 1e-6f && light_hit(L, sp.P, bdir, bt, lightPdf))) {
+    float bt, lightPdf, cv = 1.f;
+    bool hit = false;
+    if (spdf > 1e-6f) {
+      if (KIND == YK_LIGHT_AREA) hit = light_hit(L, sp.P, bdir, bt, lightPdf);
+      else hit = spot_hit(L, sp.P, bdir, bt, lightPdf, cv);
+    }
+    if (!hit) {
       put_slot(B, slot, 0, black);
       continue;
     }
-    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // bt > 1e-10
+    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0
     if (!(lightPdf > 1e-6f)) {
       put_slot(B, slot, SL_TRACED, black);
       continue;
@@ -2529,12 +2713,13 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
     const float w = m2 / (l2 + m2);
     if (B.ts) {  // lcol *= scol first (mcintegrator.cc:180)
       put_slot(B, slot, SL_TRACED | SL_ADDS, C3(surf.r * W, surf.g * W, surf.b * W));
-      put_aux(B, slot, w, 0.f, 0.f, 0.f);
+      put_aux(B, slot, w, 0.f, 0.f, KIND == YK_LIGHT_SPOT ? cv : 0.f);
       continue;
     }
     // compiled form of "surfCol * lcol * w * W": R,G ((surf*W)*lcol)*w, B (surf*W)*(w*lcol)
+    const c3 lc = KIND == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
     put_slot(B, slot, SL_TRACED | SL_ADDS,
-             C3(((surf.r * W) * lcol.r) * w, ((surf.g * W) * lcol.g) * w, (surf.b * W) * (w * lcol.b)));
+             C3(((surf.r * W) * lc.r) * w, ((surf.g * W) * lc.g) * w, (surf.b * W) * (w * lc.b)));
   }
   return nr;
 }
@@ -2585,7 +2770,7 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // the ones forced to 5 waves (YK_BOUNCE_WAVES, 640-thread blocks): since the
 // round-5 combined variant that is +1.5 % on the headline, the round-3 loss
 // (spills of 124-200 B per lane) predates their register diet.
-template <bool DIFF>
+template <bool DIFF, bool XL>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
                                                        unsigned long long* __restrict__ qword) {
   // The material records in LDS: per-lane reads of constant memory (the
@@ -2641,7 +2826,7 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
         const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
         int k0 = 0;
         for (int l = 0; l < R.nlights; ++l) {
-          nr += gen_light<DIFF>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats);
+          nr += gen_light<DIFF, XL>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats);
           k0 += c_lights[l].nslots;
         }
         kend = k0;
@@ -2690,7 +2875,7 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
 // (0 + invNS*ccol) + invNS*ccol2 (mcintegrator.cc:116-191); Dirac: 0 + v.
 // Contribution of an unoccluded slot under transparent shadows: the light
 // colour times the shadow ray's filter, then the reference's products.
-__device__ __forceinline__ c3 slot_value_ts(const Batch& B, long long slot, int kind, c3 lcol) {
+__device__ __forceinline__ c3 slot_value_ts(const Batch& B, long long slot, int kind, c3 lcol, bool spot = false) {
   const c3 a = get_contrib(B, slot);
   const float4 x = *reinterpret_cast<const float4*>(B.sl_aux + 4 * slot);
   const c3 sc = C3(B.s_filt[3 * slot], B.s_filt[3 * slot + 1], B.s_filt[3 * slot + 2]);
@@ -2698,6 +2883,7 @@ __device__ __forceinline__ c3 slot_value_ts(const Batch& B, long long slot, int 
     const c3 lc = cmul(C3(x.y, x.z, x.w), sc);
     return C3((lc.r * a.r) * x.x, (lc.g * a.g) * x.x, a.b * (lc.b * x.x));
   }
+  if (spot) lcol = cscale(x.w, lcol);  // a soft spot's ls.col / lcol: color * falloff (gen_sampled)
   const c3 lc = cmul(lcol, sc);
   if (kind == 1) {  // light sample: ((surf*lcol)*k) [*w]
     const c3 sl = cmul(a, lc);
@@ -2709,7 +2895,7 @@ __device__ __forceinline__ c3 slot_value_ts(const Batch& B, long long slot, int 
 }
 
 __device__ __forceinline__ c3 resolve_light(const Batch& B, long long c, int k0, int li) {
-  if (c_lights[li].type != YK_LIGHT_AREA) {
+  if (!light_sampled(c_lights[li])) {
     const long long slot = slot_of(B, c, k0);
     c3 col = C3(0.f, 0.f, 0.f);
     if ((B.sl_flags[slot] & SL_ADDS) && !B.s_occl[slot])
@@ -2717,13 +2903,16 @@ __device__ __forceinline__ c3 resolve_light(const Batch& B, long long c, int k0,
                            : get_contrib(B, slot));
     return col;
   }
-  const int n = c_lights[li].samples;
+  // n light samples, then the BSDF (MIS) half of the lights that have one
+  // (nslots = 2n: area, soft spot; a sphere light has nslots = n)
+  const int n = c_lights[li].samples, nk = c_lights[li].nslots;
+  const bool spot = c_lights[li].type == YK_LIGHT_SPOT;
   const float invNS = 1.f / (float)n;
   c3 ccol = C3(0.f, 0.f, 0.f), ccol2 = C3(0.f, 0.f, 0.f);
-  for (int i = 0; i < 2 * n; ++i) {
+  for (int i = 0; i < nk; ++i) {
     const long long slot = slot_of(B, c, k0 + i);
     if ((B.sl_flags[slot] & SL_ADDS) && !B.s_occl[slot]) {
-      const c3 v = B.ts ? slot_value_ts(B, slot, i < n ? 1 : 2, C3(c_lights[li].color[0], c_lights[li].color[1], c_lights[li].color[2]))
+      const c3 v = B.ts ? slot_value_ts(B, slot, i < n ? 1 : 2, C3(c_lights[li].color[0], c_lights[li].color[1], c_lights[li].color[2]), spot)
                         : get_contrib(B, slot);
       if (i < n) ccol = cadd(ccol, v);
       else ccol2 = cadd(ccol2, v);
@@ -2731,7 +2920,7 @@ __device__ __forceinline__ c3 resolve_light(const Batch& B, long long c, int k0,
   }
   c3 col = C3(0.f, 0.f, 0.f);
   col = cadd(col, cscale(invNS, ccol));
-  col = cadd(col, cscale(invNS, ccol2));
+  if (nk > n) col = cadd(col, cscale(invNS, ccol2));  // "if(canIntersect)", mcintegrator.cc:156-192
   return col;
 }
 
@@ -2783,7 +2972,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
 // (pathtracer.cc:189-298): estimateOneDirectLight shadow rays, emission,
 // and the BSDF sample of the next segment. One thread per live path (entry
 // qi of the input bounce queue, owned by camera sample c).
-template <bool DIFF>
+template <bool DIFF, bool XL>
 __global__ void __launch_bounds__(bounce_block(DIFF))
 __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES))) k_shade_bounce(DScene S, Batch B, RenderConst R,
                                                       const unsigned long long* __restrict__ qin_word, int depth,
@@ -2843,8 +3032,8 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
         // compiler reads its record with scalar loads instead of per-lane
         // vector loads (which go through the texture path that limits this
         // kernel, PMC TD busy 0.9)
-        if (R.nlights == 1) nr = gen_light<DIFF>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced);
-        else nr = gen_light<DIFF>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
+        if (R.nlights == 1) nr = gen_light<DIFF, XL>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced);
+        else nr = gen_light<DIFF, XL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
         kend = c_lights[lnum].nslots;
         if (nr) put_org(B, c, sp.P);
         if (R.nlights > 1) B.lsel[c] = lnum;  // one light: the resolve knows it is light 0
@@ -2905,6 +3094,22 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
     st_ray(&B.q_rays[qin ^ 1][qn], nxt);
     B.q_owner[qin ^ 1][qn] = (int)c;
   }
+}
+
+// The shading kernels' instantiation: DIFF (diffuse-only materials) and XL
+// (the scene holds a spot or sphere light). With the spot and sphere code in
+// every instantiation k_shade_primary grew from 105 / 123 to 117 / 132 VGPRs
+// (the general one from 4 to 3 waves per SIMD) and k_shade_bounce, held at 96,
+// spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
+// therefore run kernels that leave that code out (XL = false), as scenes
+// with plain diffuse materials leave out the component loop.
+inline auto shade_primary_fn(bool diff, bool xl) {
+  return xl ? (diff ? k_shade_primary<true, true> : k_shade_primary<false, true>)
+            : (diff ? k_shade_primary<true, false> : k_shade_primary<false, false>);
+}
+inline auto shade_bounce_fn(bool diff, bool xl) {
+  return xl ? (diff ? k_shade_bounce<true, true> : k_shade_bounce<false, true>)
+            : (diff ? k_shade_bounce<true, false> : k_shade_bounce<false, false>);
 }
 
 // pathCol += lcol*throughput; throughput *= scol of the next segment. One
@@ -3680,6 +3885,7 @@ struct yk_device {
   DScene S{};
   int ntris = 0, max_depth = 0, nlights = 0, sum_light_slots = 0;
   bool spec = false;  // some material has SPECULAR|FILTER components: recursion pipeline
+  bool xl_lights = false;  // the scene holds a spot or sphere light (shading kernels' XL instantiation)
   bool diff_only = false;  // every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>)
   yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
   void* abort_user = nullptr;
@@ -3903,6 +4109,47 @@ DLight make_dirac_light(const yk_dirac_light_state& L) {
   }
   D.radius = L.radius;
   D.infinite = L.infinite;
+  return D;
+}
+
+// spotLight_t members as yk_spot_light_state holds them (spotlight.cc:46-60)
+DLight make_spot_light(const yk_spot_light_state& L) {
+  DLight D{};
+  D.type = YK_LIGHT_SPOT;
+  D.soft = L.soft_shadows ? 1 : 0;
+  D.samples = D.soft ? L.samples : 1;
+  D.nslots = D.soft ? 2 * L.samples : 1;  // soft: cone samples + BSDF (MIS) samples
+  for (int k = 0; k < 3; ++k) {
+    D.pos[k] = L.position[k];
+    D.dir[k] = L.dir[k];
+    D.ndir[k] = L.ndir[k];
+    D.du[k] = L.du[k];
+    D.dv[k] = L.dv[k];
+    D.color[k] = L.color[k];
+  }
+  D.cos_start = L.cos_start;
+  D.cos_end = L.cos_end;
+  D.icos_diff = L.icos_diff;
+  D.fuzzy = L.shadow_fuzzyness;
+  D.photon_only = L.photon_only ? 1 : 0;
+  return D;
+}
+
+// sphereLight_t members (spherelight.cc:56-61); canIntersect() is false, so
+// an estimate takes `samples` shadow slots and no BSDF (MIS) half
+DLight make_sphere_light(const yk_sphere_light_state& L) {
+  DLight D{};
+  D.type = YK_LIGHT_SPHERE;
+  D.samples = L.samples;
+  D.nslots = L.samples;
+  for (int k = 0; k < 3; ++k) {
+    D.pos[k] = L.center[k];
+    D.color[k] = L.color[k];
+  }
+  D.radius = L.radius;
+  D.sq_radius = L.square_radius;
+  D.sq_radius_eps = L.square_radius_epsilon;
+  D.area = L.area;
   return D;
 }
 
@@ -4394,13 +4641,10 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   {
     int slots = 0;  // shadow slots per doLightEstimation sweep (DLight.nslots)
     for (size_t i = 0; i < S.light_states.size(); ++i) {
-      if (S.light_kind[i] != YK_LIGHT_AREA) {
-        slots += 1;
-      } else if (S.light_states[i].samples < 1) {
-        return set_error(YK_ERR_ARG, "light samples must be >= 1");
-      } else {
-        slots += 2 * S.light_states[i].samples;
-      }
+      const int n = light_slots(S, i);  // 1 for a Dirac light, else from the light's samples
+      if (n < 1) return set_error(YK_ERR_ARG, "light samples must be >= 1");
+      if (n > 8192) return set_error(YK_ERR_UNSUPPORTED, "too many light samples per shading point");
+      slots += n;
     }
     if (slots > 8192) return set_error(YK_ERR_UNSUPPORTED, "too many light samples per shading point");
   }
@@ -4469,12 +4713,19 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   for (size_t i = 0; i < S.light_states.size(); ++i) {
     if (S.light_kind[i] == YK_LIGHT_AREA) {
       lights.push_back(make_light(S.light_states[i]));
+    } else if (S.light_kind[i] == YK_LIGHT_SPOT) {
+      lights.push_back(make_spot_light(S.spot_states[i]));
+    } else if (S.light_kind[i] == YK_LIGHT_SPHERE) {
+      lights.push_back(make_sphere_light(S.sphere_states[i]));
     } else {
       lights.push_back(make_dirac_light(S.dirac_states[i]));
       if (lights.back().type == YK_LIGHT_DIRECTIONAL) directional_photon_frame(lights.back(), S.tree.bound);
     }
     sum_slots += lights.back().nslots;
   }
+  d->xl_lights = false;
+  for (const DLight& L : lights)
+    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) d->xl_lights = true;
   d->sum_light_slots = sum_slots;
   d->lights_host = lights;
   d->pm_ready = false;
@@ -5060,7 +5311,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
         HIPCHK(hipMemsetAsync(d->spec_words.p, 0, d->spec_words.n * sizeof(unsigned long long), P.stream));
         launch = 0;
         trace(true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
-        hipLaunchKernelGGL(d->diff_only ? k_shade_primary<true> : k_shade_primary<false>, dim3(grid_for(n, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, Bc, Rc, n, qw(0, 0));
+        hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights), dim3(grid_for(n, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, Bc, Rc, n, qw(0, 0));
         HIPCHK(hipGetLastError());
         trace(false, shadow_src(Bc), Bc.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, Bc.s_occl);
         hipLaunchKernelGGL(k_resolve_primary, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, n);
@@ -5076,7 +5327,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
             const unsigned long long* in_w = qw(isub, depth - 1);
             unsigned long long* out_w = qw(isub, depth);
             trace(true, ray_src(Bc.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, Bc.q_hits[qin], nullptr);
-            hipLaunchKernelGGL(d->diff_only ? k_shade_bounce<true> : k_shade_bounce<false>, dim3(grid_for(n, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bc, Rc, in_w, depth,
+            hipLaunchKernelGGL(shade_bounce_fn(d->diff_only, d->xl_lights), dim3(grid_for(n, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bc, Rc, in_w, depth,
                                isub, qin, out_w);
             HIPCHK(hipGetLastError());
             trace(false, shadow_src(Bc), Bc.s_idx, RayCount{out_w, 0, 0}, nullptr, Bc.s_occl);
@@ -5121,7 +5372,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
     }
     if (!d->spec) {
     trace(true, ray_src(B.p_rays), nullptr, RayCount{nullptr, 0, nc}, B.p_hits, nullptr);
-    hipLaunchKernelGGL(d->diff_only ? k_shade_primary<true> : k_shade_primary<false>, dim3(grid_for(nc, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, B, R, nc, qw(0, 0));
+    hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights), dim3(grid_for(nc, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, B, R, nc, qw(0, 0));
     HIPCHK(hipGetLastError());
     if (!merged) {
       trace(false, shadow_src(B), B.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, B.s_occl);
@@ -5148,7 +5399,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
           Bd = merged_region(B, depth);
           Bd.mq_words = qw(0, 0);
         }
-        hipLaunchKernelGGL(d->diff_only ? k_shade_bounce<true> : k_shade_bounce<false>, dim3(grid_for(nc, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bd, R, in_w, depth, isub,
+        hipLaunchKernelGGL(shade_bounce_fn(d->diff_only, d->xl_lights), dim3(grid_for(nc, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bd, R, in_w, depth, isub,
                            qin, out_w);
         HIPCHK(hipGetLastError());
         if (!merged) {

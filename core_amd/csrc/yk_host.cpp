@@ -182,9 +182,21 @@ int yk_scene_add_curve(yk_scene* s, const float* points, int32_t npoints, int32_
 
 int yk_scene_add_light(yk_scene* s, const yk_light* l) {
   if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_light: NULL argument");
-  if (l->type != YK_LIGHT_AREA && l->type != YK_LIGHT_POINT && l->type != YK_LIGHT_DIRECTIONAL)
+  if (l->type != YK_LIGHT_AREA && l->type != YK_LIGHT_POINT && l->type != YK_LIGHT_DIRECTIONAL &&
+      l->type != YK_LIGHT_SPOT && l->type != YK_LIGHT_SPHERE)
     return set_error(YK_ERR_UNSUPPORTED, "light type not supported");
   if (l->type == YK_LIGHT_AREA && l->samples < 1) return set_error(YK_ERR_ARG, "area light needs samples >= 1");
+  if (l->type == YK_LIGHT_SPOT) {
+    if (l->soft_shadows && l->samples < 1) return set_error(YK_ERR_ARG, "soft-shadow spot light needs samples >= 1");
+    if (l->from[0] == l->to[0] && l->from[1] == l->to[1] && l->from[2] == l->to[2])
+      return set_error(YK_ERR_ARG, "spot light needs from != to");
+    if (!(l->cone_angle > 0.f && l->cone_angle <= 180.f))
+      return set_error(YK_ERR_ARG, "spot light needs cone_angle in (0, 180]");
+  }
+  if (l->type == YK_LIGHT_SPHERE) {
+    if (l->samples < 1) return set_error(YK_ERR_ARG, "sphere light needs samples >= 1");
+    if (!(l->radius > 0.f)) return set_error(YK_ERR_ARG, "sphere light needs radius > 0");
+  }
   YK_GUARD_BEGIN
   s->s.add_light(*l);
   return YK_OK;
@@ -213,8 +225,47 @@ int yk_scene_add_dirac_light_state(yk_scene* s, const yk_dirac_light_state* l) {
 int yk_scene_get_dirac_light_state(const yk_scene* s, int32_t i, yk_dirac_light_state* out) {
   if (!s || !out || i < 0 || i >= (int32_t)s->s.dirac_states.size())
     return set_error(YK_ERR_ARG, "yk_scene_get_dirac_light_state: bad arguments");
-  if (s->s.light_kind[i] == YK_LIGHT_AREA) return set_error(YK_ERR_STATE, "light is an area light");
+  if (s->s.light_kind[i] != YK_LIGHT_POINT && s->s.light_kind[i] != YK_LIGHT_DIRECTIONAL)
+    return set_error(YK_ERR_STATE, "light is not a point or directional light");
   *out = s->s.dirac_states[i];
+  return YK_OK;
+}
+
+int yk_scene_add_spot_light_state(yk_scene* s, const yk_spot_light_state* l) {
+  if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_spot_light_state: NULL argument");
+  if (l->soft_shadows && l->samples < 1) return set_error(YK_ERR_ARG, "soft-shadow spot light needs samples >= 1");
+  YK_GUARD_BEGIN
+  yk_spot_light_state c = *l;
+  c.soft_shadows = c.soft_shadows ? 1 : 0;
+  c.photon_only = c.photon_only ? 1 : 0;
+  s->s.add_spot_light_state(c);
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_spot_light_state(const yk_scene* s, int32_t i, yk_spot_light_state* out) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.spot_states.size())
+    return set_error(YK_ERR_ARG, "yk_scene_get_spot_light_state: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_SPOT) return set_error(YK_ERR_STATE, "light is not a spot light");
+  *out = s->s.spot_states[i];
+  return YK_OK;
+}
+
+int yk_scene_add_sphere_light_state(yk_scene* s, const yk_sphere_light_state* l) {
+  if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_sphere_light_state: NULL argument");
+  if (l->samples < 1) return set_error(YK_ERR_ARG, "sphere light needs samples >= 1");
+  if (!(l->radius > 0.f)) return set_error(YK_ERR_ARG, "sphere light needs radius > 0");
+  YK_GUARD_BEGIN
+  s->s.add_sphere_light_state(*l);
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_sphere_light_state(const yk_scene* s, int32_t i, yk_sphere_light_state* out) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.sphere_states.size())
+    return set_error(YK_ERR_ARG, "yk_scene_get_sphere_light_state: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_SPHERE) return set_error(YK_ERR_STATE, "light is not a sphere light");
+  *out = s->s.sphere_states[i];
   return YK_OK;
 }
 

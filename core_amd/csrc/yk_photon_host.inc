@@ -94,6 +94,11 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
   if (!pt && p->integrator != YK_INTEGRATOR_PHOTON)
     return set_error(YK_ERR_ARG, "yk_photon_build: integrator must be photonmapping or pathtracing");
   if (!pt && d->nlights < 1) return set_error(YK_ERR_STATE, "photon mapping: the scene has no lights");
+  for (const DLight& L : d->lights_host)  // emitPhoton of these lights is not on the path
+    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE)
+      return set_error(YK_ERR_UNSUPPORTED,
+                       "yk_photon_build: the scene holds a spot or sphere light, whose photon emission is not "
+                       "supported (direct lighting and path tracing without photon caustics are)");
   if (!pt && q.photons <= 0) return set_error(YK_ERR_ARG, "photons must be > 0");
   if (!pt && (q.search < 1 || q.search > kMaxSearch)) return set_error(YK_ERR_UNSUPPORTED, "search must be in [1, 256]");
   if (q.caustic_mix < 1 || q.caustic_mix > kMaxSearch) return set_error(YK_ERR_UNSUPPORTED, "caustic_mix must be in [1, 256]");

@@ -45,7 +45,92 @@ __global__ void k_qmc_probe(int fn, const void* in, const uint32_t* in2, long lo
   }
 }
 
+// yk_debug_light_probe: the shading kernels' own light functions (dirac_illum,
+// light_illum / spot_illum / sphere_illum, light_hit / spot_hit / sphere_hit)
+// on light li of the bound constants; col as gen_light / gen_sampled form it
+__global__ void k_light_probe(int li, int fn, const float* in, long long n, float* out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const DLight& L = c_lights[li];
+  float* o = out + YK_LIGHT_PROBE_STRIDE * i;
+  for (int k = 0; k < YK_LIGHT_PROBE_STRIDE; ++k) o[k] = 0.f;
+  const c3 lcol = C3(L.color[0], L.color[1], L.color[2]);
+  v3 dir = V3(0.f, 0.f, 0.f);
+  float tmax = 0.f, pdf = 0.f, cv = 1.f;
+  c3 col = C3(0.f, 0.f, 0.f);
+  if (fn == YK_LIGHT_PROBE_ILLUMINATE) {
+    const bool dirac = L.type == YK_LIGHT_POINT || L.type == YK_LIGHT_DIRECTIONAL || L.type == YK_LIGHT_SPOT;
+    if (!(dirac && dirac_illum(L, ld3(in + 3 * i), dir, tmax, col))) return;
+  } else if (fn == YK_LIGHT_PROBE_ILLUM_SAMPLE) {
+    const float* x = in + 5 * i;
+    bool ok = false;
+    if (L.type == YK_LIGHT_AREA) ok = light_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf);
+    else if (L.type == YK_LIGHT_SPOT) ok = spot_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf, cv);
+    else if (L.type == YK_LIGHT_SPHERE) ok = sphere_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf);
+    if (!ok) return;
+    col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
+  } else {
+    const float* x = in + 6 * i;
+    bool ok = false;
+    float t = 0.f;
+    if (L.type == YK_LIGHT_AREA) ok = light_hit(L, ld3(x), ld3(x + 3), t, pdf);
+    else if (L.type == YK_LIGHT_SPOT) ok = spot_hit(L, ld3(x), ld3(x + 3), t, pdf, cv);
+    else if (L.type == YK_LIGHT_SPHERE) ok = sphere_hit(L, ld3(x), ld3(x + 3), pdf);
+    if (!ok) return;
+    col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
+    o[0] = 1.f;
+    o[1] = t;
+    o[2] = L.type == YK_LIGHT_SPHERE ? 0.f : 1.f;
+    o[3] = col.r;
+    o[4] = col.g;
+    o[5] = col.b;
+    o[6] = pdf;
+    return;
+  }
+  o[0] = 1.f;
+  o[1] = dir.x;
+  o[2] = dir.y;
+  o[3] = dir.z;
+  o[4] = tmax;
+  o[5] = col.r;
+  o[6] = col.g;
+  o[7] = col.b;
+  o[8] = pdf;
+}
+
 }  // namespace
+
+extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t fn, const float* in, int64_t n,
+                                    float* out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_light_probe: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !in || !out || n < 0 || n > (1ll << 24)) return set_error(YK_ERR_ARG, "yk_debug_light_probe: bad arguments");
+  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_light_probe: no scene uploaded");
+  if (light_index < 0 || light_index >= d->nlights)
+    return set_error(YK_ERR_ARG, "yk_debug_light_probe: no such light");
+  size_t in_f;
+  switch (fn) {
+    case YK_LIGHT_PROBE_ILLUMINATE: in_f = 3; break;
+    case YK_LIGHT_PROBE_ILLUM_SAMPLE: in_f = 5; break;
+    case YK_LIGHT_PROBE_INTERSECT: in_f = 6; break;
+    default: return set_error(YK_ERR_ARG, "yk_debug_light_probe: unknown function");
+  }
+  if (n == 0) return YK_OK;
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  bind_constants(d);
+  DBuf<float> din, dout;
+  din.ensure((size_t)n * in_f);
+  dout.ensure((size_t)n * YK_LIGHT_PROBE_STRIDE);
+  HIPCHK(hipMemcpy(din.p, in, (size_t)n * in_f * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_light_probe, dim3(grid_for(n)), dim3(256), 0, d->stream, (int)light_index, (int)fn,
+                     (const float*)din.p, (long long)n, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(out, dout.p, (size_t)n * YK_LIGHT_PROBE_STRIDE * sizeof(float), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
 
 extern "C" int yk_debug_qmc_probe(yk_device* d, int32_t fn, const void* in, const uint32_t* in2, int64_t n,
                                   void* out) {

@@ -108,6 +108,21 @@ class Scene:
                        direction=A.f3(*direction), radius=radius, infinite=int(infinite))
         A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
 
+    def add_spot_light(self, from_, to, color=(1, 1, 1), power=1.0, cone_angle=45.0, blend=0.15,
+                       soft_shadows=False, samples=8, shadow_fuzzyness=1.0, photon_only=False):
+        """spotlight (spotlight.cc:284-305); cone_angle is the cone's half angle in degrees"""
+        l = A.yk_light(type=A.YK_LIGHT_SPOT, color=A.f3(*color), power=power, samples=samples,
+                       from_=A.f3(*from_), to=A.f3(*to), cone_angle=cone_angle, blend=blend,
+                       soft_shadows=int(soft_shadows), shadow_fuzzyness=shadow_fuzzyness,
+                       photon_only=int(photon_only))
+        A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
+
+    def add_sphere_light(self, from_, radius=1.0, color=(1, 1, 1), power=1.0, samples=4):
+        """spherelight (spherelight.cc:196-213), without its "object" link"""
+        l = A.yk_light(type=A.YK_LIGHT_SPHERE, color=A.f3(*color), power=power, samples=samples,
+                       from_=A.f3(*from_), radius=radius)
+        A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
+
     def set_background(self, color, power=1.0):
         """constant background (textureback.cc:206-218, ibl off); None removes it"""
         if color is None:
@@ -160,14 +175,28 @@ class Scene:
     def add_dirac_light_state(self, st):
         A.check(A.lib().yk_scene_add_dirac_light_state(self._p, C.byref(st)))
 
+    def add_spot_light_state(self, st):
+        A.check(A.lib().yk_scene_add_spot_light_state(self._p, C.byref(st)))
+
+    def add_sphere_light_state(self, st):
+        A.check(A.lib().yk_scene_add_sphere_light_state(self._p, C.byref(st)))
+
     def light_states(self):
-        """Per light: yk_area_light_state or yk_dirac_light_state."""
+        """Per light: yk_area_light_state, yk_dirac_light_state, yk_spot_light_state
+        or yk_sphere_light_state (each getter answers YK_ERR_STATE for the other kinds)."""
+        L = A.lib()
+        getters = ((A.yk_area_light_state, L.yk_scene_get_area_light_state),
+                   (A.yk_dirac_light_state, L.yk_scene_get_dirac_light_state),
+                   (A.yk_spot_light_state, L.yk_scene_get_spot_light_state),
+                   (A.yk_sphere_light_state, L.yk_scene_get_sphere_light_state))
         out = []
         for k in range(self.info().nlights):
-            m = A.yk_area_light_state()
-            if A.lib().yk_scene_get_area_light_state(self._p, k, C.byref(m)) == A.YK_ERR_STATE:
-                m = A.yk_dirac_light_state()
-                A.check(A.lib().yk_scene_get_dirac_light_state(self._p, k, C.byref(m)))
+            for cls, get in getters:
+                m = cls()
+                rc = get(self._p, k, C.byref(m))
+                if rc != A.YK_ERR_STATE:
+                    break
+            A.check(rc)
             out.append(m)
         return out
 

@@ -67,7 +67,7 @@ typedef struct yk_material {
 } yk_material;
 enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 
-enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2 };
+enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2, YK_LIGHT_SPOT = 3, YK_LIGHT_SPHERE = 4 };
 typedef struct yk_light {
   int32_t type;
   /* area: areaLight_t::factory, arealight.cc:171-192 */
@@ -82,6 +82,21 @@ typedef struct yk_light {
   float direction[3];
   float radius;
   int32_t infinite;
+  /* spot: spotLight_t::factory (spotlight.cc:284-305): from [0,0,0], to
+   * [0,0,-1], color [1,1,1], power [1], cone_angle [45, degrees, the half
+   * angle of the cone], blend [0.15], photon_only [0], soft_shadows [0],
+   * shadow_fuzzyness ("shadowFuzzyness") [1], samples [8]; a zero-initialised
+   * struct must set them.
+   * sphere: sphereLight_t::factory (spherelight.cc:196-213): from [0,0,0]
+   * (the centre), color [1,1,1], power [1], radius [1], samples [4]; its
+   * "object" link is not on the path. Appended fields only: the offsets
+   * above are what earlier callers compiled against. */
+  float to[3];
+  float cone_angle;
+  float blend;
+  int32_t soft_shadows;
+  float shadow_fuzzyness;
+  int32_t photon_only;
 } yk_light;
 
 /* perspectiveCam_t bokeh shapes and bias (perspectiveCamera.h:33-34) */
@@ -329,6 +344,28 @@ typedef struct yk_dirac_light_state { /* pointLight_t / directionalLight_t membe
   int32_t infinite;
 } yk_dirac_light_state;
 
+typedef struct yk_spot_light_state { /* spotLight_t members after its ctor (spotlight.cc:63-75) */
+  float position[3];
+  float dir[3], ndir[3];    /* ndir = (from - to).normalize(), dir = -ndir              */
+  float du[3], dv[3];       /* createCS(dir, du, dv), vector3d.h:316-334                */
+  float cos_start, cos_end; /* fCos of the inner / outer angle (cos_start >= cos_end)   */
+  float icos_diff;          /* 1.0 / (cosStart - cosEnd)                                */
+  float color[3];           /* color * power                                            */
+  int32_t soft_shadows;     /* 0: a Dirac light (one shadow ray); 1: illumSample + intersect */
+  float shadow_fuzzyness;
+  int32_t samples;          /* read when soft_shadows != 0                              */
+  int32_t photon_only;      /* illuminate / illumSample return false                    */
+} yk_spot_light_state;
+
+typedef struct yk_sphere_light_state { /* sphereLight_t members after its ctor (spherelight.cc:64-72) */
+  float center[3];
+  float radius, square_radius;
+  float square_radius_epsilon; /* square_radius * 1.000003815 (in double)               */
+  float area;                  /* square_radius * 4.0 * M_PI (in double)                */
+  float color[3];              /* color * power                                         */
+  int32_t samples;
+} yk_sphere_light_state;
+
 typedef struct yk_camera_state { /* perspectiveCam_t after setAxis (perspectiveCamera.cc:57-71) */
   float position[3], vright[3], vup[3], vto[3], cam_z[3];
   float near_p[3], far_p[3]; /* near_plane.p / far_plane.p (camera.h:54-57)            */
@@ -348,6 +385,16 @@ int yk_scene_add_area_light_state(yk_scene* s, const yk_area_light_state* l);
  * per estimate, mcintegrator.cc:85-100 */
 int yk_scene_add_dirac_light_state(yk_scene* s, const yk_dirac_light_state* l);
 int yk_scene_get_dirac_light_state(const yk_scene* s, int32_t i, yk_dirac_light_state* out);
+/* spot light: Dirac (one shadow ray) unless soft_shadows, then `samples`
+ * cone samples and as many BSDF (MIS) samples per estimate; sphere light:
+ * `samples` cone samples and no MIS half (sphereLight_t::canIntersect() is
+ * false, spherelight.cc:49). YK_ERR_STATE from a getter when light i is of
+ * another kind. Photon emission of these lights is not on the path:
+ * yk_photon_build refuses scenes that hold one. */
+int yk_scene_add_spot_light_state(yk_scene* s, const yk_spot_light_state* l);
+int yk_scene_get_spot_light_state(const yk_scene* s, int32_t i, yk_spot_light_state* out);
+int yk_scene_add_sphere_light_state(yk_scene* s, const yk_sphere_light_state* l);
+int yk_scene_get_sphere_light_state(const yk_scene* s, int32_t i, yk_sphere_light_state* out);
 /* constBackground_t (textureback.cc:187-218, "constant", ibl off): camera
  * rays that miss add color*power. rgb NULL removes the background. */
 int yk_scene_set_background(yk_scene* s, const float* rgb, float power);
@@ -479,8 +526,9 @@ int yk_device_build_tree(yk_device* d, const yk_scene* s, int32_t flags, yk_tree
  * aim rays at the split planes of the tree actually traversed. */
 int yk_device_export_tree(yk_device* d, uint32_t* nodes, int64_t node_cap, uint32_t* leaf, int64_t leaf_cap,
                           int64_t* nnodes_out, int64_t* nleaf_out);
-/* Test-only hooks (the watchdog's tree damage) are declared in
- * yk_test_hooks.h, not here, and are disabled unless YK_DEBUG_HOOKS=1. */
+/* Test-only hooks (the watchdog's tree damage, the lights' function probe)
+ * are declared in yk_test_hooks.h and yk_test_hooks_light.h, not here, and
+ * are disabled unless YK_DEBUG_HOOKS=1. */
 
 #ifdef __cplusplus
 }

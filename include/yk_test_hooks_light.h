@@ -1,0 +1,35 @@
+/* yk_test_hooks_light.h -- test-only probe of the lights' device functions.
+ * Like yk_test_hooks.h it is NOT part of the product ABI (include/yk_api.h),
+ * and the hook refuses to run (YK_ERR_UNSUPPORTED) unless the process
+ * environment has YK_DEBUG_HOOKS=1. */
+#ifndef YK_TEST_HOOKS_LIGHT_H
+#define YK_TEST_HOOKS_LIGHT_H
+#include "yk_api.h"
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Runs, in a kernel on `d`, the device functions the shading kernels call
+ * for light `light_index` of the resident scene, over n host-supplied inputs
+ * (`in`: floats per input as listed). `out` gets YK_LIGHT_PROBE_STRIDE floats
+ * per input, laid out as listed and zero where the function wrote nothing
+ * (ok = 0 or 1 as a float; a refused sample leaves its record at zero):
+ *   ILLUMINATE    in: P[3]             -> ok, dir[3], tmax, col[3]
+ *                 light_t::illuminate: point, directional and spot lights
+ *                 (a spot light answers whether or not it has soft shadows);
+ *                 ok = 0 for the others, as their illuminate() returns false
+ *   ILLUM_SAMPLE  in: P[3], s1, s2     -> ok, dir[3], tmax, col[3], pdf
+ *                 light_t::illumSample: area, spot and sphere lights
+ *   INTERSECT     in: from[3], dir[3]  -> ok, t, t_set, col[3], ipdf
+ *                 light_t::intersect: area, spot and sphere lights; t_set = 0
+ *                 for a sphere light, whose intersect() never writes t
+ *                 (spherelight.cc:134-149)
+ * col is ls.col / lcol as doLightEstimation receives it. */
+enum { YK_LIGHT_PROBE_ILLUMINATE = 0, YK_LIGHT_PROBE_ILLUM_SAMPLE = 1, YK_LIGHT_PROBE_INTERSECT = 2 };
+enum { YK_LIGHT_PROBE_STRIDE = 12 };
+int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t fn, const float* in, int64_t n, float* out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* YK_TEST_HOOKS_LIGHT_H */

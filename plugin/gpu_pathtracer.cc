@@ -167,6 +167,30 @@ struct DirectionalLightLayout : public light_t {
   bool infinite;
   int majorAxis;
 };
+// spotLight_t (spotlight.cc:45-60) and sphereLight_t (spherelight.cc:55-61),
+// likewise defined in their plugins' .cc files. Unverified: this plugin is
+// not compiled in this repository's setup.
+class pdf1D_t;
+struct SpotLightLayout : public light_t {
+  point3d_t position;
+  vector3d_t dir, ndir, du, dv;
+  PFLOAT cosStart, cosEnd, icosDiff;
+  color_t color;
+  float intensity;
+  pdf1D_t* pdf;
+  float interv1, interv2;
+  bool photonOnly, softShadows;
+  float shadowFuzzy;
+  int samples;
+};
+struct SphereLightLayout : public light_t {
+  point3d_t center;
+  PFLOAT radius, square_radius, square_radius_epsilon;
+  color_t color;
+  int samples;
+  unsigned int objID;
+  float area, invArea;
+};
 struct ConstBackgroundLayout : public background_t {
   color_t color;
 };
@@ -311,8 +335,45 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
         if (yk_scene_add_dirac_light_state(ys, &d) != YK_OK) return fail();
         continue;
       }
+      if (tn == "N7yafaray11spotLight_tE" || tn == "N7yafaray13sphereLight_tE") {
+        // yk_photon_build refuses them as well: their emitPhoton is not on the path
+        if (params.integrator == YK_INTEGRATOR_PHOTON || params.caustic_type == YK_CAUSTIC_PHOTON ||
+            params.caustic_type == YK_CAUSTIC_BOTH)
+          return unsupported("spot and sphere lights run on the GPU path without photon maps only");
+        if (tn == "N7yafaray11spotLight_tE") {
+          const SpotLightLayout* sl = static_cast<const SpotLightLayout*>(l);
+          yk_spot_light_state d{};
+          put3(d.position, sl->position.x, sl->position.y, sl->position.z);
+          put3(d.dir, sl->dir.x, sl->dir.y, sl->dir.z);
+          put3(d.ndir, sl->ndir.x, sl->ndir.y, sl->ndir.z);
+          put3(d.du, sl->du.x, sl->du.y, sl->du.z);
+          put3(d.dv, sl->dv.x, sl->dv.y, sl->dv.z);
+          d.cos_start = sl->cosStart;
+          d.cos_end = sl->cosEnd;
+          d.icos_diff = sl->icosDiff;
+          put3(d.color, sl->color.R, sl->color.G, sl->color.B);
+          d.soft_shadows = sl->softShadows ? 1 : 0;
+          d.shadow_fuzzyness = sl->shadowFuzzy;
+          d.samples = sl->samples;
+          d.photon_only = sl->photonOnly ? 1 : 0;
+          if (yk_scene_add_spot_light_state(ys, &d) != YK_OK) return fail();
+        } else {
+          const SphereLightLayout* sl = static_cast<const SphereLightLayout*>(l);
+          if (sl->objID != 0) return unsupported("a sphere light bound to an object does not run on the GPU path");
+          yk_sphere_light_state d{};
+          put3(d.center, sl->center.x, sl->center.y, sl->center.z);
+          d.radius = sl->radius;
+          d.square_radius = sl->square_radius;
+          d.square_radius_epsilon = sl->square_radius_epsilon;
+          d.area = sl->area;
+          put3(d.color, sl->color.R, sl->color.G, sl->color.B);
+          d.samples = sl->samples;
+          if (yk_scene_add_sphere_light_state(ys, &d) != YK_OK) return fail();
+        }
+        continue;
+      }
       areaLight_t* al = dynamic_cast<areaLight_t*>(l);
-      if (!al) return unsupported("only area, point and directional lights run on the GPU path");
+      if (!al) return unsupported("only area, point, directional, spot and sphere lights run on the GPU path");
       yk_area_light_state s{};
       const point3d_t& c = GET(*al, AlCorner);
       const vector3d_t &x = GET(*al, AlToX), &y = GET(*al, AlToY);
