@@ -160,6 +160,26 @@ class yk_stats(C.Structure):
                 ("ms_reduce", C.c_double)]
 
 
+# include/yk_test_hooks.h: the batch planner's inputs, its plan, the last render's plan
+class yk_batch_plan_in(C.Structure):
+    _fields_ = [("slots", C.c_int32), ("bounces", C.c_int32), ("merged", C.c_int32), ("split", C.c_int32),
+                ("transp_shadows", C.c_int32), ("spec", C.c_int32), ("final_gather", C.c_int32),
+                ("spec_levels", C.c_int32), ("tile", C.c_int32), ("spp", C.c_int32), ("pipes", C.c_int32),
+                ("reserved", C.c_int32), ("owned_tiles", C.c_int64), ("target_samples", C.c_int64),
+                ("budget_bytes", C.c_int64)]
+
+
+class yk_batch_plan(C.Structure):
+    _fields_ = [("status", C.c_int32), ("tiles_per_batch", C.c_int32), ("nbatch", C.c_int32),
+                ("npipes", C.c_int32), ("regions", C.c_int32), ("kshift", C.c_int32), ("maxc", C.c_int64),
+                ("kstride", C.c_int64), ("bytes_per_sample", C.c_int64)]
+
+
+class yk_last_plan(C.Structure):
+    _fields_ = [("plan", yk_batch_plan), ("max_batches_on_pipe", C.c_int32), ("reserved", C.c_int32),
+                ("pipe_bytes", C.c_int64), ("batch_bytes", C.c_int64)]
+
+
 P = C.c_void_p
 i32, i64, u32p = C.c_int32, C.c_int64, C.POINTER(C.c_uint32)
 fp, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
@@ -232,6 +252,8 @@ SIGNATURES = {
     "yk_debug_small_scene": (C.c_int, [P, C.POINTER(i64)]),
     "yk_debug_shading_kind": (C.c_int, [P, C.POINTER(C.c_int32)]),
     "yk_debug_shadow_form": (C.c_int, [P, C.POINTER(yk_render_params), C.POINTER(C.c_int32)]),
+    "yk_debug_batch_plan": (C.c_int, [C.POINTER(yk_batch_plan_in), C.POINTER(yk_batch_plan)]),
+    "yk_debug_last_plan": (C.c_int, [P, C.POINTER(yk_last_plan)]),
 }
 
 _lib = None

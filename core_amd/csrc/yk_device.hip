@@ -3760,9 +3760,23 @@ struct Pipe {
     if (ev1) (void)hipEventDestroy(ev1);
     if (stream) (void)hipStreamDestroy(stream);
   }
+  template <class T>
+  static long long held(const DBuf<T>& b) { return (long long)(b.n * sizeof(T)); }
+  // bytes of the buffers a batch plan sizes (bind, and render_pass's
+  // final-gather buffers): what plan_batches budgets as maxc * bytes_per_sample
+  long long batch_bytes() const {
+    return held(soffs) + held(s_idx) + held(col) + held(alpha) + held(thr) + held(pathcol) + held(scol_next) +
+           held(wlast) + held(emit_b) + held(sl_contrib) + held(prim_hit) + held(pstate) + held(lsel) + held(qo0) +
+           held(qo1) + held(tile_base) + held(tiles) + held(p_rays) + held(qr0) + held(qr1) + held(s_dir) +
+           held(p_hits) + held(qh0) + held(qh1) + held(sl_flags) + held(s_occl) + held(samples) + held(sxy) +
+           held(pext) + held(psample) + held(incl) + held(caus) + held(emit0) + held(fgl) + held(fglen) + held(lkq) +
+           held(s_filt) + held(sl_aux);
+  }
+  // every device buffer of the pipe
+  long long all_bytes() const { return batch_bytes() + held(counters) + held(words) + held(ovf); }
   // regions > 1: the merged shadow launch's slot regions (camera hits + one
   // per bounce) and per-bounce path state (merged_region)
-  Batch bind(long long maxc, int K, int tiles_per_batch, bool spec = false, bool ts = false, int regions = 1) {
+  Batch bind(long long maxc, int K, int tiles_per_batch, bool spec, bool ts, int regions, bool split) {
     const long long nst = std::max(1, regions - 1);  // path-state copies
     soffs.ensure(maxc);
     col.ensure(3 * maxc);
@@ -3783,7 +3797,7 @@ struct Pipe {
     qr1.ensure(maxc);
     qh0.ensure(maxc);
     qh1.ensure(maxc);
-    s_dir.ensure(maxc * std::max(K + 1, 2 * K) * regions);  // the split form, or K 32-B rays
+    s_dir.ensure(maxc * (split ? K + 1 : 2 * K) * regions);  // K {dir, w} + one origin, or K 32-B rays (Batch)
     s_occl.ensure(maxc * K * regions);
     s_idx.ensure(maxc * K * regions);
     sl_contrib.ensure(3 * maxc * K * regions);
@@ -3821,6 +3835,7 @@ struct Pipe {
     B.samples = samples.p;
     B.sxy = sxy.p;
     B.pext = pext.p;
+    B.split = split ? 1 : 0;
     B.K = K;
     B.cap = maxc;
     B.kstride = maxc * regions;
@@ -3856,6 +3871,81 @@ inline int pipes_env() {
   const char* e = std::getenv("YK_PIPES");
   const int v = e ? std::atoi(e) : 0;
   return (v >= 1 && v <= kPipes) ? v : kPipes;
+}
+
+// The batch planner (host only, no device state: yk_debug_batch_plan runs it
+// as it stands). Cuts the shard's tiles into batches of whole tiles, about
+// `target_samples` camera samples each (default 32M: each trace launch ends
+// in a tail of long rays, which large batches amortise), capped so that the
+// batch buffers of all pipes stay within `budget_bytes`; the cap itself is
+// floored at 1M samples, an explicit target is not (one-tile batches: tests).
+// Returns nullptr, or the reason the frame cannot be planned
+// (out.status = YK_ERR_UNSUPPORTED).
+constexpr long long kNodeBytes = 116;  // specular node store, per node
+const char* plan_batches(const yk_batch_plan_in& in, yk_batch_plan& out) {
+  out = yk_batch_plan{};
+  out.status = YK_ERR_UNSUPPORTED;
+  if (in.slots > (1 << 20) || in.bounces < 0 || in.bounces > 62) return "too many shadow slots or bounces";
+  const int K = std::max(1, in.slots);
+  const int pipes_cfg = std::min(kPipes, std::max(1, in.pipes));
+  const long long owned = std::max<long long>(0, in.owned_tiles);
+  const int regions = in.merged ? in.bounces + 1 : 1;
+  out.regions = regions;
+  // one pipe's batch buffers per camera sample (Pipe::bind): 232 B of sample
+  // state, rays, hits and bounce queues, 32 B of path state, 48 B of
+  // final-gather state (fgl, fglen, lkq) and 18 B of specular-entry state are
+  // the 400 B; 2 B per slot of margin; per region 50 B per slot (32-B ray,
+  // contribution, flag, result, queue entry), 34 B + a 16-B origin per sample
+  // in the split form; + 32 B of path state per extra region; transparent
+  // shadows add 28 B per slot (s_filt, sl_aux)
+  const long long region_bytes = in.split ? 34ll * K + 16 : 50ll * K;
+  const long long bytes_per_sample = 400 + 2ll * K + region_bytes + (long long)(regions - 1) * (region_bytes + 32) +
+                                     (in.transp_shadows ? 28ll * K : 0);
+  out.bytes_per_sample = bytes_per_sample;
+  const long long target_env = in.target_samples > 0 ? in.target_samples : (32ll << 20);
+  const long long target =
+      std::min(target_env, std::max(1ll << 20, std::max<long long>(0, in.budget_bytes) / pipes_cfg / bytes_per_sample));
+  const long long tile_samples = (long long)in.tile * in.tile * in.spp;
+  if (in.tile < 1 || in.spp < 1) return "empty tile";
+  // specular recursion: generation g holds recursion level g; every node has
+  // at most two children, so a batch of nc camera samples needs at most
+  // nc * (2^(L+1) - 1) nodes, L = spec_levels
+  const long long spec_worst = (2ll << std::max(0, std::min(in.spec_levels, 19))) - 1;
+  if (in.spec && spec_worst * tile_samples * kNodeBytes > (48ll << 30))
+    return "raydepth too large for the tile size / spp (node store > 48 GB)";
+  const long long target_spec = in.spec ? std::min(target, (12ll << 30) / (kNodeBytes * spec_worst)) : target;
+  // at least one batch per pipeline when the frame has the tiles for it -- a
+  // frame of 2 full batches (C2: 1024 tiles of 64K samples) leaves two
+  // pipelines idle (C2 8388 -> 8700 Mrays/s, headline and hair unchanged);
+  // photon mapping too since round 6 (its 16-spp bench frame in 4 batches
+  // instead of 1: 2123-2129 against 2086-2090 Mrays/s; 6 or 8 batches lost:
+  // 1874-1944; round 2 had measured 1572 -> 1537 before the final-gather
+  // pipeline took its present form)
+  const long long tiles_fill = in.spec ? LLONG_MAX : (owned + pipes_cfg - 1) / pipes_cfg;
+  long long tiles_per_batch =
+      std::max<long long>(1, std::min<long long>(INT_MAX, std::min(target_spec / tile_samples, tiles_fill)));
+  // the trace kernels hold a ray's index in a signed int (-1: no ray) and
+  // read a launch's ray count as one: camera-sample indices, shadow-slot
+  // indices (k * kstride + r * maxc + c) and the merged launch's queue count
+  // (at most maxc * K * regions) stay below 2^31; a split shadow-queue entry
+  // holds k above the origin index r * maxc + c in 32 bits (Batch)
+  auto index_fits = [&](long long mc) {
+    if (mc >= (1ll << 31)) return false;
+    int kshift = 0;
+    while ((1ll << kshift) < mc * regions) ++kshift;
+    return mc * (long long)K * regions < (1ll << 31) && kshift <= 31 && ((long long)(K - 1) << kshift) < (1ll << 32);
+  };
+  while (tiles_per_batch > 1 && !index_fits(tiles_per_batch * tile_samples)) tiles_per_batch /= 2;
+  const long long maxc = tiles_per_batch * tile_samples;
+  if (!index_fits(maxc)) return "one tile holds too many samples (tile^2 * spp * shadow slots * regions >= 2^31)";
+  out.tiles_per_batch = (int)tiles_per_batch;
+  out.maxc = maxc;
+  out.kstride = maxc * regions;
+  while ((1ll << out.kshift) < out.kstride) ++out.kshift;
+  out.nbatch = (int)((owned + tiles_per_batch - 1) / tiles_per_batch);
+  out.npipes = in.spec ? 1 : std::min(pipes_cfg, std::max(1, out.nbatch));
+  out.status = YK_OK;
+  return nullptr;
 }
 
 struct yk_device {
@@ -3932,6 +4022,10 @@ struct yk_device {
   DBuf<int4> tiles_dev;
   DBuf<int> base_dev, pix_dev, pmap_dev, rank_dev;
   DBuf<uint8_t> flags_dev;
+  // the last render's batch plan (yk_debug_last_plan)
+  yk_batch_plan last_plan{};
+  bool last_plan_valid = false;
+  int last_max_batches = 0;
   hipStream_t mstream[kMaxMultiDev] = {};
   hipEvent_t mevent[kMaxMultiDev] = {};
   ~yk_device() {
@@ -5023,20 +5117,9 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
   R.pass_off = ps.off;
   R.ps = (R.spec || R.multipass) ? 1 : 0;
   const int K = std::max(1, d->sum_light_slots);
-  // specular recursion: generation g holds recursion level g; every node has
-  // at most two children, so a batch of nc camera samples needs at most
-  // nc * (2^(L+1) - 1) nodes, L = min(raydepth, 19)
+  // specular recursion: the node store holds min(raydepth, 19) levels (plan_batches)
   const int spec_levels = d->spec ? std::max(0, std::min(p->raydepth, 19)) : 0;
   const long long spec_worst = (2ll << spec_levels) - 1;
-  constexpr long long kNodeBytes = 116;
-  // batch = whole tiles, about YK_BATCH_SAMPLES camera samples (default 32M:
-  // each trace launch ends in a tail of long rays, which large batches
-  // amortise), capped so the buffers of all pipes stay within YK_BATCH_GB
-  static const long long target_env = [] {
-    const char* e = std::getenv("YK_BATCH_SAMPLES");
-    const long long v = e ? std::atoll(e) : 0;
-    return v > 0 ? v : (32ll << 20);
-  }();
   // merged shadow launch (k_resolve_merged): path tracing without specular
   // recursion, photon maps or transparent shadows, one sub-path; YK_MERGE=0
   // (read per render: A/B runs, tests) keeps one any-hit launch per bounce
@@ -5045,7 +5128,6 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
     return !(e && std::atoi(e) == 0) && p->integrator == YK_INTEGRATOR_PATH && !d->spec && !pt_cmap &&
            !p->transp_shadows && p->path_samples <= 1 && p->bounces >= 1;
   }();
-  const int regions = merged ? p->bounces + 1 : 1;
   R.merged = merged ? 1 : 0;
   // HBM for the batch buffers of all pipes (YK_BATCH_GB, default 64 of the
   // 288 GB, 192 with the merged launch's slot regions: C2's eight slots per
@@ -5056,43 +5138,37 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
     const long long v = e ? std::atoll(e) : 0;
     return (v > 0 && v <= 240) ? v : 0ll;
   }();
-  const long long batch_bytes = (batch_gb_env ? batch_gb_env : (merged ? 192ll : 64ll)) << 30;
   const bool split = shadow_split(d, p);
-  // per region: 50 B per slot (32-B ray, contribution, flag, result, queue
-  // entry), 34 B + a 16-B origin per sample in the split form; + 32 B of path
-  // state per sample and extra region
-  const long long region_bytes = split ? 34ll * K + 16 : 50ll * K;
-  const long long bytes_per_sample = 400 + 2ll * K + region_bytes + (long long)(regions - 1) * (region_bytes + 32);
-  const int pipes_cfg = pipes_env();
-  const long long target = std::max(1ll << 20, std::min(target_env, batch_bytes / pipes_cfg / bytes_per_sample));
-  const long long tile_samples = (long long)F.tile * F.tile * spp;
-  if (d->spec && spec_worst * tile_samples * kNodeBytes > (48ll << 30))
-    return set_error(YK_ERR_UNSUPPORTED, "raydepth too large for the tile size / spp (node store > 48 GB)");
-  const long long target_spec = d->spec ? std::min(target, (12ll << 30) / (kNodeBytes * spec_worst)) : target;
-  // at least one batch per pipeline when the frame has the tiles for it -- a
-  // frame of 2 full batches (C2: 1024 tiles of 64K samples) leaves two
-  // pipelines idle (C2 8388 -> 8700 Mrays/s, headline and hair unchanged);
-  // photon mapping too since round 6 (its 16-spp bench frame in 4 batches
-  // instead of 1: 2123-2129 against 2086-2090 Mrays/s; 6 or 8 batches lost:
-  // 1874-1944; round 2 had measured 1572 -> 1537 before the final-gather
-  // pipeline took its present form)
-  const long long tiles_fill = d->spec ? LLONG_MAX : ((long long)owned.size() + pipes_cfg - 1) / pipes_cfg;
-  int tiles_per_batch = (int)std::max<long long>(1, std::min(target_spec / tile_samples, tiles_fill));
-  // camera-sample indices are 32-bit on the device, shadow-slot indices
-  // (k * kstride + r * maxc + c) 32-bit, and a shadow-queue entry holds k
-  // above the origin index r * maxc + c in 32 bits (Batch)
-  auto index_fits = [&](long long mc) {
-    int kshift = 0;
-    while ((1ll << kshift) < mc * regions) ++kshift;
-    return mc < (1ll << 31) && mc * (long long)std::max(K, 1) * regions < (1ll << 32) && kshift <= 31 &&
-           ((long long)std::max(K - 1, 0) << kshift) < (1ll << 32);
-  };
-  while (tiles_per_batch > 1 && !index_fits((long long)tiles_per_batch * tile_samples)) tiles_per_batch /= 2;
-  const long long maxc = (long long)tiles_per_batch * tile_samples;
-  if (!index_fits(maxc))
-    return set_error(YK_ERR_UNSUPPORTED, "one tile holds too many samples (tile^2 * spp * shadow slots >= 2^32)");
-  const int nbatch = (int)((owned.size() + tiles_per_batch - 1) / tiles_per_batch);
-  const int npipes = d->spec ? 1 : std::min(pipes_cfg, std::max(1, nbatch));
+  // batches, pipes and every buffer size: plan_batches. YK_BATCH_SAMPLES and
+  // YK_PIPES are read on every render (A/B runs, tests)
+  yk_batch_plan_in pin{};
+  pin.slots = K;
+  pin.bounces = merged ? p->bounces : 0;
+  pin.merged = merged ? 1 : 0;
+  pin.split = split ? 1 : 0;
+  pin.transp_shadows = p->transp_shadows ? 1 : 0;
+  pin.spec = d->spec ? 1 : 0;
+  pin.final_gather = R.pm_fg;
+  pin.spec_levels = spec_levels;
+  pin.tile = F.tile;
+  pin.spp = spp;
+  pin.pipes = pipes_env();
+  pin.owned_tiles = (long long)owned.size();
+  {
+    const char* e = std::getenv("YK_BATCH_SAMPLES");
+    pin.target_samples = e ? std::atoll(e) : 0;
+  }
+  pin.budget_bytes = (batch_gb_env ? batch_gb_env : (merged ? 192ll : 64ll)) << 30;
+  yk_batch_plan plan;
+  if (const char* why = plan_batches(pin, plan)) return set_error(YK_ERR_UNSUPPORTED, why);
+  const int regions = plan.regions;
+  const int tiles_per_batch = plan.tiles_per_batch;
+  const long long maxc = plan.maxc;
+  const int nbatch = plan.nbatch;
+  const int npipes = plan.npipes;
+  d->last_plan = plan;
+  d->last_plan_valid = true;
+  d->last_max_batches = (nbatch + npipes - 1) / npipes;
   const bool path = p->integrator == YK_INTEGRATOR_PATH;
   // final gathering: hits 0..fg_bounces of each gather path, queue words up to fg_bounces + 1
   const int bounces = path ? R.bounces : (R.pm_fg ? p->photon.fg_bounces + 1 : 0);
@@ -5182,8 +5258,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
     const int nb_here = (nbatch - pi + npipes - 1) / npipes;
     P.words.ensure((size_t)(2 * kAccWords + (d->spec ? 0 : words_per_batch * nb_here)));
     HIPCHK(hipMemsetAsync(P.words.p, 0, P.words.n * sizeof(unsigned long long), P.stream));
-    Bp[pi] = P.bind(maxc, K, tiles_per_batch, R.ps != 0, p->transp_shadows != 0, regions);
-    Bp[pi].split = split ? 1 : 0;
+    Bp[pi] = P.bind(maxc, K, tiles_per_batch, R.ps != 0, p->transp_shadows != 0, regions, split);
     if (R.pm_fg) {
       P.fgl.ensure(3 * maxc);
       P.fglen.ensure(maxc);

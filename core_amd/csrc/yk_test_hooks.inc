@@ -201,3 +201,25 @@ extern "C" int yk_debug_shadow_form(yk_device* d, const yk_render_params* p, int
   *split = shadow_split(d, p) ? 1 : 0;
   return YK_OK;
 }
+
+extern "C" int yk_debug_batch_plan(const yk_batch_plan_in* in, yk_batch_plan* out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_batch_plan: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!in || !out) return set_error(YK_ERR_ARG, "yk_debug_batch_plan: bad arguments");
+  if (const char* why = plan_batches(*in, *out)) return set_error(YK_ERR_UNSUPPORTED, why);
+  return YK_OK;
+}
+
+extern "C" int yk_debug_last_plan(yk_device* d, yk_last_plan* out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_last_plan: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !out) return set_error(YK_ERR_ARG, "yk_debug_last_plan: bad arguments");
+  if (!d->last_plan_valid) return set_error(YK_ERR_STATE, "yk_debug_last_plan: no render yet");
+  *out = yk_last_plan{};
+  out->plan = d->last_plan;
+  out->max_batches_on_pipe = d->last_max_batches;
+  // batches go round-robin from pipe 0, so pipe 0 ran the most
+  out->pipe_bytes = d->pipe[0].all_bytes();
+  out->batch_bytes = d->pipe[0].batch_bytes();
+  return YK_OK;
+}

@@ -60,6 +60,60 @@ int yk_debug_shading_kind(yk_device* d, int32_t* diff_only);
  * rays. YK_ERR_UNSUPPORTED unless YK_DEBUG_HOOKS=1. */
 int yk_debug_shadow_form(yk_device* d, const yk_render_params* p, int32_t* split);
 
+/* The batch planner of a render: how the shard's tiles are cut
+ * into batches and dealt onto pipes, and the sizes every per-batch buffer and
+ * every 32-bit device index follow from. Plain numbers in, plain numbers out. */
+typedef struct yk_batch_plan_in {
+  int32_t slots;          /* K: shadow slots per camera sample (sum over the lights), >= 1 */
+  int32_t bounces;        /* path-tracing bounces (the merged launch has bounces + 1 slot regions) */
+  int32_t merged;         /* 1: merged shadow launch */
+  int32_t split;          /* 1: split shadow-slot form (yk_debug_shadow_form) */
+  int32_t transp_shadows; /* 1: transparent shadows (filter buffers per slot) */
+  int32_t spec;           /* 1: specular recursion (node store, one pipe) */
+  int32_t final_gather;   /* 1: photon mapping with final gathering */
+  int32_t spec_levels;    /* recursion levels of the node store, min(raydepth, 19); 0 without spec */
+  int32_t tile;           /* tile edge in pixels */
+  int32_t spp;            /* camera samples per pixel of the pass */
+  int32_t pipes;          /* YK_PIPES, 1..4 */
+  int32_t reserved;
+  int64_t owned_tiles;    /* tiles of this shard */
+  int64_t target_samples; /* YK_BATCH_SAMPLES; <= 0: unset (32M) */
+  int64_t budget_bytes;   /* HBM for the batch buffers of all pipes (YK_BATCH_GB) */
+} yk_batch_plan_in;
+
+typedef struct yk_batch_plan {
+  int32_t status;          /* YK_OK, or YK_ERR_UNSUPPORTED when one tile cannot be planned */
+  int32_t tiles_per_batch;
+  int32_t nbatch;
+  int32_t npipes;          /* pipes that run a batch: min(pipes, nbatch), 1 with spec */
+  int32_t regions;         /* slot regions per batch: bounces + 1 merged, else 1 */
+  int32_t kshift;          /* split queue entries: bits of the origin index */
+  int64_t maxc;            /* camera samples a batch's buffers are sized for */
+  int64_t kstride;         /* slot stride of k: regions * maxc */
+  int64_t bytes_per_sample;/* budgeted bytes of one pipe's batch buffers per camera sample */
+} yk_batch_plan;
+
+/* The planner itself, a pure host function: needs no device (and no GPU in
+ * the machine). out->status and the return value carry the same code.
+ * YK_ERR_UNSUPPORTED unless YK_DEBUG_HOOKS=1 (then out is left untouched). */
+int yk_debug_batch_plan(const yk_batch_plan_in* in, yk_batch_plan* out);
+
+/* The last render on d (the last pass of an adaptive render): the plan it
+ * used, the largest number of batches one pipe ran, and what that pipe's
+ * buffers hold now: pipe_bytes = the sum over all its device buffers,
+ * batch_bytes = the part the plan sizes (everything but the traversal stack
+ * overflow area, the counters and the per-launch words, which follow the
+ * launch grid and the launch count, not the batch). YK_ERR_STATE before the
+ * first render; YK_ERR_UNSUPPORTED unless YK_DEBUG_HOOKS=1. */
+typedef struct yk_last_plan {
+  yk_batch_plan plan;
+  int32_t max_batches_on_pipe;
+  int32_t reserved;
+  int64_t pipe_bytes;
+  int64_t batch_bytes;
+} yk_last_plan;
+int yk_debug_last_plan(yk_device* d, yk_last_plan* out);
+
 #ifdef __cplusplus
 }
 #endif
