@@ -114,7 +114,12 @@ def _compare(gpu_device, s, name, rays, ranges, ref_hits, ref_occ, hits, occ, in
         # family aims at them) and on axis-aligned scenes; answers the
         # reference tree loses (its clipped leaves) are rare on random rays and
         # concentrate on rays that start on its own split planes (37 of 1284 on
-        # the Cornell box). The device answer itself is brute-force checked above.
+        # the Cornell box). Those 37 are all undecided under the float64
+        # classifier of tests/bruteforce.py (none is a decided hit or miss):
+        # origins lying on a wall with the float64 hit at t = +-0, and rays
+        # running inside a wall's plane that meet another surface on its edge;
+        # the whole family passes check_closest on the reference tree. The
+        # device answer itself is brute-force checked above.
         cap_bad, cap_lost = FAMILY_CAPS[fam]
         print(f"  {fam}: {len(bad)} of {b - a} differ, checked {min(len(bad), BRUTE_PER_FAMILY)}: "
               f"{f_ties} ties, {f_lost} lost by the reference tree")
