@@ -125,7 +125,10 @@ class yk_render_params(C.Structure):
                 ("aa_pixelwidth", C.c_float), ("tile_size", C.c_int32),
                 ("transp_background", C.c_int32), ("aa_inc_samples", C.c_int32), ("aa_threshold", C.c_float),
                 ("photon", yk_photon_params), ("transp_shadows", C.c_int32), ("shadow_depth", C.c_int32),
-                ("filter_width", C.c_float), ("tile_order", C.POINTER(C.c_int32)), ("tile_order_len", C.c_int32)]
+                ("filter_width", C.c_float), ("tile_order", C.POINTER(C.c_int32)), ("tile_order_len", C.c_int32),
+                # directlighting's own options: ambient occlusion and photon caustics
+                ("do_ao", C.c_int32), ("ao_samples", C.c_int32), ("ao_distance", C.c_float), ("ao_color", f3),
+                ("dl_caustics", C.c_int32)]
 
     def copy(self):
         p = yk_render_params()

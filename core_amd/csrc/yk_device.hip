@@ -2263,7 +2263,8 @@ enum : uint8_t { SL_TRACED = 1, SL_ADDS = 2 };
 struct Batch;
 __device__ __forceinline__ long long slot_of(const Batch& B, long long c, int k);
 // prim_hit flags
-enum : int { PH_HIT = 1, PH_DIFFUSE = 2, PH_LIGHT = 4 };
+// (PH_AOEMIT: ambient occlusion on an emitting diffuse material, k_resolve_ao)
+enum : int { PH_HIT = 1, PH_DIFFUSE = 2, PH_LIGHT = 4, PH_AOEMIT = 8 };
 // path state bits
 // (PS_EMIT: emit_b holds this bounce's emission; otherwise it is zero and
 // not stored. 256: clear of the final-gather bits, yk_photon.inc)
@@ -2724,6 +2725,61 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
   return nr;
 }
 
+// Ambient occlusion of direct lighting (directlight.cc:142): the parameters
+// of mcIntegrator_t::sampleAmbientOcclusion. The AO rays of a shading point
+// own the n shadow slots k0 .. k0 + n - 1 after the lights' (k0 = the scene's
+// light slots), in loop order.
+struct AOConst {
+  int n;         // aoSamples (rayDivision is 1 on this path); 0: off
+  int k0;        // first AO slot
+  float dist;    // aoDist: the rays' tmax
+  float col[3];  // aoCol
+};
+constexpr unsigned kAOFlags = BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_REFLECT;
+
+// mcIntegrator_t::sampleAmbientOcclusion (mcintegrator.cc:629-683), split at
+// its isShadowed call like gen_light: sample i's ray (tmin YAF_SHADOW_BIAS,
+// tmax aoDist, the form of a light-sample ray) goes to slot k0 + i with
+// "aoCol * surfCol * cos * W" in source order (the compiled order of this
+// function is not pinned); under transparent shadows aoCol * scol comes first,
+// so the slot keeps surfCol and the aux record {cos, W}. A sample() that
+// returns early (no component matches, or their widths sum below 1e-5) leaves
+// W = 0 and the previous direction: its term is +0 whatever the ray meets,
+// and the slot traces nothing.
+template <bool DIFF>
+__device__ __forceinline__ int gen_ao(const Batch& B, long long c, const AOConst& A, const DMat& M, const SurfPt& sp,
+                                      v3 wo, unsigned pixelSample, unsigned soffs, unsigned long long& traced) {
+  const c3 black = C3(0.f, 0.f, 0.f);
+  const int n = A.n;
+  const unsigned offs = (unsigned)(n * (int)pixelSample) + soffs;
+  Halton h2, h3;
+  hal_start(h2, 2u, offs - 1u);
+  hal_start(h3, 3u, offs - 1u);
+  int nr = 0;
+  for (int i = 0; i < n; ++i) {
+    const float s1 = hal_next(h2), s2 = hal_next(h3);
+    const long long slot = slot_of(B, c, A.k0 + i);
+    float W = 0.f, pdf = 0.f;
+    bool ok;
+    v3 dir = V3(0.f, 0.f, 0.f);
+    const c3 surf = mat_sample<DIFF>(M, sp, wo, dir, s1, s2, kAOFlags, pdf, W, ok);
+    if (!ok) {
+      put_slot(B, slot, 0, black);
+      continue;
+    }
+    nr += emit_shadow<false>(B, slot, sp.P, dir, A.dist, A.k0 + i, traced);
+    const float cs = fabsf(vdot(sp.N, dir));
+    if (B.ts) {
+      put_slot(B, slot, SL_TRACED | SL_ADDS, surf);
+      put_aux(B, slot, cs, W, 0.f, 0.f);
+      continue;
+    }
+    put_slot(B, slot, SL_TRACED | SL_ADDS,
+             C3(((A.col[0] * surf.r) * cs) * W, ((A.col[1] * surf.g) * cs) * W, ((A.col[2] * surf.b) * cs) * W));
+  }
+  return nr;
+}
+
 // Writes the traced slots [0,kend) of sample c to the shadow queue from
 // `base`, in slot order (bit mask for the first 64 slots, flags beyond).
 __device__ __forceinline__ void flush_shadow(const Batch& B, long long c, int kend, int nr, unsigned base,
@@ -2770,9 +2826,11 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // the ones forced to 5 waves (YK_BOUNCE_WAVES, 640-thread blocks): since the
 // round-5 combined variant that is +1.5 % on the headline, the round-3 loss
 // (spills of 124-200 B per lane) predates their register diet.
-template <bool DIFF, bool XL>
+// AO: direct lighting with ambient occlusion (gen_ao) -- an instantiation of
+// its own, so the others carry none of its code; A is read by it alone.
+template <bool DIFF, bool XL, bool AO>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
-                                                       unsigned long long* __restrict__ qword) {
+                                                       unsigned long long* __restrict__ qword, AOConst A) {
   // The material records in LDS: per-lane reads of constant memory (the
   // lanes' materials differ) go through the vector-memory path, which limits
   // the shading kernels (C2 PMC: TD busy 0.87-0.90 of the CU's cycles, waves
@@ -2830,6 +2888,11 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
           k0 += c_lights[l].nslots;
         }
         kend = k0;
+        if constexpr (AO) {
+          nr += gen_ao<DIFF>(B, c, A, M, sp, wo, s, B.soffs[c], traced);
+          kend = A.k0 + A.n;
+          if (M.flags & BSDF_EMIT) ph |= PH_AOEMIT;
+        }
         if (nr) put_org(B, c, sp.P);
         if (R.integrator == YK_INTEGRATOR_PATH) {
           B.wlast[c] = 0.f;
@@ -2937,6 +3000,60 @@ __global__ void __launch_bounds__(256) k_resolve_primary(Batch B, RenderConst R,
   B.col[3 * c] = B.col[3 * c] + dl.r;
   B.col[3 * c + 1] = B.col[3 * c + 1] + dl.g;
   B.col[3 * c + 2] = B.col[3 * c + 2] + dl.b;
+}
+
+// col += sampleAmbientOcclusion (directlight.cc:142), after the direct light
+// and the caustic estimate: the unoccluded AO slots' terms in loop order from
+// 0, then col / (float)n. An emitting material also adds emit * s.pdf per
+// sample ahead of that sample's term (mcintegrator.cc:666-669); its entries
+// (PH_AOEMIT) sample the material again for s.pdf rather than every slot
+// keeping a value that almost no scene reads.
+__global__ void __launch_bounds__(256) k_resolve_ao(DScene S, Batch B, RenderConst R, AOConst A, long long nc) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const int ph = B.prim_hit[c];
+  if (!(ph & PH_DIFFUSE)) return;
+  c3 col = C3(0.f, 0.f, 0.f);
+  const c3 aoc = C3(A.col[0], A.col[1], A.col[2]);
+  const bool emits = (ph & PH_AOEMIT) != 0;
+  SurfPt sp{};
+  v3 wo = V3(0.f, 0.f, 0.f);
+  c3 em = C3(0.f, 0.f, 0.f);
+  Halton h2{}, h3{};
+  if (emits) {
+    const yk_ray r = B.p_rays[c];
+    const v3 from = V3(r.from[0], r.from[1], r.from[2]), dir = V3(r.dir[0], r.dir[1], r.dir[2]);
+    sp = make_surface(S, from, dir, B.p_hits[c]);
+    wo = vneg(dir);
+    em = mat_emit(c_mats[sp.mat], sp, wo, true);
+    const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
+    const unsigned offs = (unsigned)(A.n * (int)s) + B.soffs[c];
+    hal_start(h2, 2u, offs - 1u);
+    hal_start(h3, 3u, offs - 1u);
+  }
+  for (int i = 0; i < A.n; ++i) {
+    if (emits) {  // col += material->emit(state, sp, wo) * s.pdf
+      const float s1 = hal_next(h2), s2 = hal_next(h3);
+      float W = 0.f, pdf = 0.f;
+      bool ok;
+      v3 wi = V3(0.f, 0.f, 0.f);
+      (void)mat_sample<false>(c_mats[sp.mat], sp, wo, wi, s1, s2, kAOFlags, pdf, W, ok);
+      col = cadd(col, cscale(pdf, em));
+    }
+    const long long slot = slot_of(B, c, A.k0 + i);
+    if (!(B.sl_flags[slot] & SL_ADDS) || B.s_occl[slot]) continue;
+    c3 v = get_contrib(B, slot);
+    if (B.ts) {  // aoCol * scol * surfCol * cos * W
+      const float4 x = *reinterpret_cast<const float4*>(B.sl_aux + 4 * slot);
+      const c3 as = cmul(aoc, C3(B.s_filt[3 * slot], B.s_filt[3 * slot + 1], B.s_filt[3 * slot + 2]));
+      v = C3(((as.r * v.r) * x.x) * x.y, ((as.g * v.g) * x.x) * x.y, ((as.b * v.b) * x.x) * x.y);
+    }
+    col = cadd(col, v);
+  }
+  const float fn = (float)A.n;
+  B.col[3 * c] = B.col[3 * c] + col.r / fn;
+  B.col[3 * c + 1] = B.col[3 * c + 1] + col.g / fn;
+  B.col[3 * c + 2] = B.col[3 * c + 2] + col.b / fn;
 }
 
 // First segment of sub-paths isub >= 1 (sub-path 0 is fused into
@@ -3103,9 +3220,12 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
 // spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
 // therefore run kernels that leave that code out (XL = false), as scenes
 // with plain diffuse materials leave out the component loop.
-inline auto shade_primary_fn(bool diff, bool xl) {
-  return xl ? (diff ? k_shade_primary<true, true> : k_shade_primary<false, true>)
-            : (diff ? k_shade_primary<true, false> : k_shade_primary<false, false>);
+inline auto shade_primary_fn(bool diff, bool xl, bool ao) {
+  if (ao)
+    return xl ? (diff ? k_shade_primary<true, true, true> : k_shade_primary<false, true, true>)
+              : (diff ? k_shade_primary<true, false, true> : k_shade_primary<false, false, true>);
+  return xl ? (diff ? k_shade_primary<true, true, false> : k_shade_primary<false, true, false>)
+            : (diff ? k_shade_primary<true, false, false> : k_shade_primary<false, false, false>);
 }
 inline auto shade_bounce_fn(bool diff, bool xl) {
   return xl ? (diff ? k_shade_bounce<true, true> : k_shade_bounce<false, true>)
@@ -4488,9 +4608,15 @@ size_t lookup_lds_bytes(int depth) { return (size_t)std::max(1, depth) * 64 * (s
 // the kernels that have the split form (not universal, big-leaf or
 // transparent-shadow); YK_SPLIT=0/1 (read per render: A/B runs, tests)
 // forces either form where it exists
+// Direct lighting's ambient occlusion: ao_samples more slots per shading
+// point. They take the split form with the lights' slots: every AO ray of a
+// point shares its origin and bias, so 32 rays are 32 * 16 + 16 B, not 32 * 32.
+inline int ao_slots(const yk_render_params* p) {
+  return (p->integrator == YK_INTEGRATOR_DIRECT && p->do_ao) ? std::max(0, p->ao_samples) : 0;
+}
 bool shadow_split(const yk_device* d, const yk_render_params* p) {
   const char* e = std::getenv("YK_SPLIT");
-  const int K = std::max(1, d->sum_light_slots);
+  const long long K = std::max<long long>(1, (long long)d->sum_light_slots + ao_slots(p));
   return (e ? std::atoi(e) != 0 : K >= 4) && !d->S.uni && !d->big_leaves && !p->transp_shadows;
 }
 
@@ -5047,10 +5173,21 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
   // pathtracing with photon caustics reads the caustic map its preprocess built
   const bool pt_cmap = p->integrator == YK_INTEGRATOR_PATH &&
                        (p->caustic_type == YK_CAUSTIC_PHOTON || p->caustic_type == YK_CAUSTIC_BOTH);
-  if ((pm || pt_cmap) && (!d->pm_ready || d->pm_integrator != p->integrator))
+  // direct lighting's own options (directlight.cc:137-142): photon caustics
+  // under pathtracing's rules, ambient occlusion with its own shadow slots
+  const bool direct = p->integrator == YK_INTEGRATOR_DIRECT;
+  const bool dl_cmap = direct && p->dl_caustics != 0;
+  const bool cmap = pt_cmap || dl_cmap;
+  const bool ao = direct && p->do_ao != 0;
+  if ((pm || cmap) && (!d->pm_ready || d->pm_integrator != p->integrator))
     return set_error(YK_ERR_STATE, "photon maps: call yk_photon_build for this integrator first (preprocess)");
-  if ((pm || pt_cmap) && std::memcmp(&p->photon, &d->pm_params, sizeof(yk_photon_params)) != 0)
+  if ((pm || cmap) && std::memcmp(&p->photon, &d->pm_params, sizeof(yk_photon_params)) != 0)
     return set_error(YK_ERR_STATE, "photon mapping: the maps were built with different photon parameters");
+  if (ao && p->ao_samples < 1) return set_error(YK_ERR_ARG, "AO_samples must be >= 1");
+  if (ao && !(std::isfinite(p->ao_distance) && p->ao_distance > 0.f))
+    return set_error(YK_ERR_ARG, "AO_distance must be finite and > 0");
+  if (ao && (long long)d->sum_light_slots + p->ao_samples > 8192)
+    return set_error(YK_ERR_UNSUPPORTED, "too many shadow slots per shading point (light samples + AO_samples > 8192)");
   if (p->integrator == YK_INTEGRATOR_PATH && (p->bounces < 1 || 4 * p->bounces + 4 >= 50))
     return set_error(YK_ERR_UNSUPPORTED, "bounces must be in [1, 11]");
   if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
@@ -5100,7 +5237,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
   if (p->transp_shadows && (p->shadow_depth < 0 || p->shadow_depth > 8))
     return set_error(YK_ERR_UNSUPPORTED, "shadowDepth must be in [0, 8] with transpShad");
   if (R.pm_fg) R.nsub = std::max(1, p->photon.fg_samples);  // nSampl = max(1, nPaths / rayDivision)
-  const PMConst PMC = (pm || pt_cmap) ? pm_const(d, p->photon) : PMConst{};
+  const PMConst PMC = (pm || cmap) ? pm_const(d, p->photon) : PMConst{};
   R.bounces = p->bounces;
   R.integrator = p->integrator;
   R.transp_bg = p->transp_background;
@@ -5116,7 +5253,15 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
   R.multipass = ps.multipass ? 1 : 0;
   R.pass_off = ps.off;
   R.ps = (R.spec || R.multipass) ? 1 : 0;
-  const int K = std::max(1, d->sum_light_slots);
+  // the lights' slots, then the AO rays' (gen_ao)
+  const int K = std::max(1, d->sum_light_slots + ao_slots(p));
+  AOConst AOC{};
+  if (ao) {
+    AOC.n = p->ao_samples;
+    AOC.k0 = d->sum_light_slots;
+    AOC.dist = p->ao_distance;
+    for (int k = 0; k < 3; ++k) AOC.col[k] = p->ao_color[k];
+  }
   // specular recursion: the node store holds min(raydepth, 19) levels (plan_batches)
   const int spec_levels = d->spec ? std::max(0, std::min(p->raydepth, 19)) : 0;
   const long long spec_worst = (2ll << spec_levels) - 1;
@@ -5370,6 +5515,10 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
       hipLaunchKernelGGL(k_pt_caustic, dim3(grid_for(n, 64)), dim3(64), 0, P.stream, d->S, Bc, PMC, n);
       HIPCHK(hipGetLastError());
     };
+    auto resolve_ao = [&](const Batch& Bc, const RenderConst& Rc, long long n) {
+      hipLaunchKernelGGL(k_resolve_ao, dim3(grid_for(n)), dim3(256), 0, P.stream, d->S, Bc, Rc, AOC, n);
+      HIPCHK(hipGetLastError());
+    };
     TileList TL{tiles_dev.p + (size_t)bi * tiles_per_batch, base_dev.p + (size_t)bi * (tiles_per_batch + 1),
                 (int)std::min<size_t>(tiles_per_batch, owned.size() - (size_t)bi * tiles_per_batch),
                 ps.flags ? pix_dev.p + pix_off[bi] : nullptr};
@@ -5386,7 +5535,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
         HIPCHK(hipMemsetAsync(d->spec_words.p, 0, d->spec_words.n * sizeof(unsigned long long), P.stream));
         launch = 0;
         trace(true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
-        hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights), dim3(grid_for(n, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, Bc, Rc, n, qw(0, 0));
+        hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights, ao), dim3(grid_for(n, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, Bc, Rc, n, qw(0, 0), AOC);
         HIPCHK(hipGetLastError());
         trace(false, shadow_src(Bc), Bc.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, Bc.s_occl);
         hipLaunchKernelGGL(k_resolve_primary, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, n);
@@ -5413,7 +5562,8 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
           }
         }
         if (pm) pm_entries(Bc, Rc, n);
-        if (pt_cmap) pt_caustic(Bc, n);
+        if (cmap) pt_caustic(Bc, n);
+        if (ao) resolve_ao(Bc, Rc, n);
         hipLaunchKernelGGL(k_finish_spec, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, NS, node_base, n);
         HIPCHK(hipGetLastError());
         hipLaunchKernelGGL(k_spawn, dim3(grid_for(n)), dim3(256), 0, P.stream, d->S, Bc, Rc, NS, node_base, n);
@@ -5447,7 +5597,7 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
     }
     if (!d->spec) {
     trace(true, ray_src(B.p_rays), nullptr, RayCount{nullptr, 0, nc}, B.p_hits, nullptr);
-    hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights), dim3(grid_for(nc, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, B, R, nc, qw(0, 0));
+    hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights, ao), dim3(grid_for(nc, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, B, R, nc, qw(0, 0), AOC);
     HIPCHK(hipGetLastError());
     if (!merged) {
       trace(false, shadow_src(B), B.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, B.s_occl);
@@ -5455,7 +5605,8 @@ static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, i
       HIPCHK(hipGetLastError());
     }
     if (pm) pm_entries(B, R, nc);
-    if (pt_cmap) pt_caustic(B, nc);
+    if (cmap) pt_caustic(B, nc);
+    if (ao) resolve_ao(B, R, nc);
     // sub-path index outermost: pathCol is shared across sub-paths and
     // accumulated in the reference's order (pathtracer.cc:164-298)
     for (int isub = 0; isub < (path ? nsub : 0); ++isub) {
@@ -5657,7 +5808,8 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
       return set_error(YK_ERR_STATE, "yk_render_multi: the devices hold different scenes (upload the same scene to all)");
     const bool maps = p->integrator == YK_INTEGRATOR_PHOTON ||
                       (p->integrator == YK_INTEGRATOR_PATH &&
-                       (p->caustic_type == YK_CAUSTIC_PHOTON || p->caustic_type == YK_CAUSTIC_BOTH));
+                       (p->caustic_type == YK_CAUSTIC_PHOTON || p->caustic_type == YK_CAUSTIC_BOTH)) ||
+                      (p->integrator == YK_INTEGRATOR_DIRECT && p->dl_caustics != 0);
     if (maps && (!devs[i]->pm_ready || devs[i]->pm_integrator != p->integrator ||
                  std::memcmp(&devs[i]->pm_params, &p->photon, sizeof(yk_photon_params)) != 0))
       return set_error(YK_ERR_STATE, "yk_render_multi: device " + std::to_string(i) +

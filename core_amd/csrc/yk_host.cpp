@@ -462,6 +462,12 @@ void yk_render_params_default(yk_render_params* p) {
   q.fg_min_pathlen = 0.1f;  // = diffuseRadius
   q.show_map = 0;
   q.seed = 123212;          // myseed, vector3d.cc:185
+  // directLighting_t::factory (directlight.cc:184-252)
+  p->do_ao = 0;
+  p->ao_samples = 32;
+  p->ao_distance = 1.0f;
+  p->ao_color[0] = p->ao_color[1] = p->ao_color[2] = 1.f;
+  p->dl_caustics = 0;
 }
 
 int yk_scene_generate(yk_scene* s, const char* name, int32_t p0, int32_t p1, int32_t resx,

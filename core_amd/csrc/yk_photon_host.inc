@@ -90,9 +90,13 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
   const yk_photon_params& q = p->photon;
   // pathtracing with caustic_type photon / both: pathIntegrator_t::preprocess
   // builds only the caustic map (createCausticMap, mcintegrator.cc:197-377)
-  const bool pt = p->integrator == YK_INTEGRATOR_PATH;
+  // directlighting with "caustics" runs the same pass (directLighting_t::
+  // preprocess, directlight.cc:78-83): pt stands for "the caustic map alone"
+  const bool pt = p->integrator == YK_INTEGRATOR_PATH ||
+                  (p->integrator == YK_INTEGRATOR_DIRECT && p->dl_caustics != 0);
   if (!pt && p->integrator != YK_INTEGRATOR_PHOTON)
-    return set_error(YK_ERR_ARG, "yk_photon_build: integrator must be photonmapping or pathtracing");
+    return set_error(YK_ERR_ARG, "yk_photon_build: integrator must be photonmapping, pathtracing or directlighting "
+                                 "with caustics");
   if (!pt && d->nlights < 1) return set_error(YK_ERR_STATE, "photon mapping: the scene has no lights");
   for (const DLight& L : d->lights_host)  // emitPhoton of these lights is not on the path
     if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE)

@@ -178,6 +178,25 @@ typedef struct yk_render_params {
    * t % nshards == shard, in list order. [NULL, 0]                           */
   const int32_t* tile_order;
   int32_t tile_order_len;
+  /* directlighting's own options (directLighting_t::factory, directlight.cc:
+   * 184-252; used at directlight.cc:137-142). Read only when integrator ==
+   * YK_INTEGRATOR_DIRECT; appended, so the offsets above are what earlier
+   * callers compiled against, and a zero-initialised struct has both off.
+   * Ambient occlusion (mcIntegrator_t::sampleAmbientOcclusion, mcintegrator.cc:
+   * 629-683): ao_samples any-hit rays of length ao_distance per diffuse
+   * shading point, camera hits and specular-recursion nodes alike. do_ao != 0
+   * needs ao_samples >= 1 and a finite ao_distance > 0 (YK_ERR_ARG), and
+   * light slots + ao_samples <= 8192 (YK_ERR_UNSUPPORTED). */
+  int32_t do_ao;        /* "do_AO" [0]                                              */
+  int32_t ao_samples;   /* "AO_samples" [32]                                        */
+  float ao_distance;    /* "AO_distance" [1.0] (parsed as double, held as float aoDist) */
+  float ao_color[3];    /* "AO_color" [1,1,1]                                       */
+  /* "caustics" [0]: col += estimateCausticPhotons on diffuse hits, from the
+   * caustic map yk_photon_build makes for YK_INTEGRATOR_DIRECT with this flag
+   * set (directLighting_t::preprocess, directlight.cc:78-83), out of
+   * photon.caustic_photons ("photons"), caustic_mix, caustic_radius and
+   * bounces ("caustic_depth"), as path tracing's photon caustics do. */
+  int32_t dl_caustics;
 } yk_render_params;
 enum { YK_TILES_LINEAR = 0, YK_TILES_RANDOM = 1 };
 
@@ -497,7 +516,10 @@ typedef struct yk_photon_info {
  * yk_render_shard with p->integrator == YK_INTEGRATOR_PHOTON.
  * With p->integrator == YK_INTEGRATOR_PATH it is pathIntegrator_t::preprocess
  * for caustic_type photon / both (pathtracer.cc:76-129): only the caustic map
- * of mcIntegrator_t::createCausticMap (mcintegrator.cc:197-377). */
+ * of mcIntegrator_t::createCausticMap (mcintegrator.cc:197-377). The same
+ * pass runs for p->integrator == YK_INTEGRATOR_DIRECT with p->dl_caustics set
+ * (directLighting_t::preprocess, directlight.cc:78-83); without the flag
+ * direct lighting has no preprocess and the call returns YK_ERR_ARG. */
 int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* info);
 enum { YK_PHOTON_MAP_DIFFUSE = 0, YK_PHOTON_MAP_CAUSTIC = 1, YK_PHOTON_MAP_RADIANCE = 2 };
 /* copy a map out in photon-vector order: 9 floats per photon (pos, dir, color);

@@ -338,7 +338,8 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
       if (tn == "N7yafaray11spotLight_tE" || tn == "N7yafaray13sphereLight_tE") {
         // yk_photon_build refuses them as well: their emitPhoton is not on the path
         if (params.integrator == YK_INTEGRATOR_PHOTON || params.caustic_type == YK_CAUSTIC_PHOTON ||
-            params.caustic_type == YK_CAUSTIC_BOTH)
+            params.caustic_type == YK_CAUSTIC_BOTH ||
+            (params.integrator == YK_INTEGRATOR_DIRECT && params.dl_caustics != 0))
           return unsupported("spot and sphere lights run on the GPU path without photon maps only");
         if (tn == "N7yafaray11spotLight_tE") {
           const SpotLightLayout* sl = static_cast<const SpotLightLayout*>(l);
@@ -446,8 +447,11 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
           Y_INFO << integratorName << ": device kd-tree, " << ti.nodes << " nodes (" << ti.ms_build << " ms)" << yendl;
       }
     }
-    const bool pt_photons = params.integrator == YK_INTEGRATOR_PATH &&
-                            (params.caustic_type == YK_CAUSTIC_PHOTON || params.caustic_type == YK_CAUSTIC_BOTH);
+    // directlighting with "caustics" builds the same map in its preprocess
+    // (directlight.cc:78-83)
+    const bool pt_photons = (params.integrator == YK_INTEGRATOR_PATH &&
+                             (params.caustic_type == YK_CAUSTIC_PHOTON || params.caustic_type == YK_CAUSTIC_BOTH)) ||
+                            (params.integrator == YK_INTEGRATOR_DIRECT && params.dl_caustics != 0);
     // photon maps: every GPU builds the same maps from the same inputs (the
     // build is deterministic), so each holds a replica
     if (pt_photons) {
@@ -587,6 +591,37 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
     bool bg = true;
     pm.getParam("bg_transp", bg);
     p.transp_background = bg;
+    // The plugin replaces directLighting_t, so no live mcIntegrator_t holds
+    // useAmbientOcclusion / aoSamples / aoDist / aoCol or usePhotonCaustics /
+    // nCausPhotons / nCausSearch / causDepth / causRadius (mcintegrator.h:
+    // 70-90): they are read as directLighting_t::factory reads them, with its
+    // names, types and defaults (directlight.cc:186-237)
+    bool do_ao = false, caustics = false;
+    int ao_samples = 32, c_depth = 10, search = 100, photons = 500000;
+    double ao_dist = 1.0, c_rad = 0.25;
+    color_t ao_col(1.f);
+    pm.getParam("do_AO", do_ao);
+    pm.getParam("AO_samples", ao_samples);
+    pm.getParam("AO_distance", ao_dist);
+    pm.getParam("AO_color", ao_col);
+    pm.getParam("caustics", caustics);
+    pm.getParam("photons", photons);
+    pm.getParam("caustic_mix", search);
+    pm.getParam("caustic_depth", c_depth);
+    pm.getParam("caustic_radius", c_rad);
+    p.do_ao = do_ao;
+    p.ao_samples = ao_samples;
+    p.ao_distance = (float)ao_dist;  // float aoDist
+    p.ao_color[0] = ao_col.R;
+    p.ao_color[1] = ao_col.G;
+    p.ao_color[2] = ao_col.B;
+    p.dl_caustics = caustics;
+    if (caustics) {
+      p.photon.caustic_photons = photons;
+      p.photon.caustic_mix = search;
+      p.photon.bounces = c_depth;
+      p.photon.caustic_radius = (float)c_rad;
+    }
     auto* it = new gpuTiledIntegrator_t(p, "DirectLight");
     it->read_plugin_params(pm);
     return it;
