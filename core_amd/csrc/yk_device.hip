@@ -3829,6 +3829,13 @@ struct DBuf {
   ~DBuf() { release(); }
 };
 
+// One kernel launch, checked. (dim3 converts from a plain count.)
+template <class... KArgs, class... Args>
+void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args&&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, std::forward<Args>(args)...);
+  HIPCHK(hipGetLastError());
+}
+
 }  // namespace
 
 // One batch pipeline: a stream with its own queues, counters and scratch.
@@ -3882,8 +3889,8 @@ struct Pipe {
   }
   template <class T>
   static long long held(const DBuf<T>& b) { return (long long)(b.n * sizeof(T)); }
-  // bytes of the buffers a batch plan sizes (bind, and render_pass's
-  // final-gather buffers): what plan_batches budgets as maxc * bytes_per_sample
+  // bytes of the buffers a batch plan sizes (bind, and the final-gather
+  // buffers of bind_pipes): what plan_batches budgets as maxc * bytes_per_sample
   long long batch_bytes() const {
     return held(soffs) + held(s_idx) + held(col) + held(alpha) + held(thr) + held(pathcol) + held(scol_next) +
            held(wlast) + held(emit_b) + held(sl_contrib) + held(prim_hit) + held(pstate) + held(lsel) + held(qo0) +
@@ -4068,16 +4075,45 @@ const char* plan_batches(const yk_batch_plan_in& in, yk_batch_plan& out) {
   return nullptr;
 }
 
+// The trace kernels of one signature, as a table. k_trace_shadow_ts takes two
+// more arguments (filter colours, depth) and stays on its own
+// (enqueue_trace_ts, per_cu_ts).
+enum TraceVariant {
+  kClosest, kShadow, kShadowSplit,                                    // large trees
+  kClosestBig, kShadowBig,                                            // a leaf of 2^17 references or more
+  kShadowUni, kShadowBigUni,                                          // universal-mode scenes
+  kClosestSmall, kShadowSmall, kShadowSmallSplit, kShadowUniSmall,  // traversal data in LDS
+  kTraceVariants
+};
+using TraceKernel = void (*)(DScene, RaySrc, const unsigned*, RayCount, yk_hit*, uint8_t*, unsigned long long*,
+                             unsigned long long*, uint2*, int, int);
+struct TraceInfo {
+  TraceKernel kernel;
+  int waves;     // per workgroup
+  bool dyn_lds;  // small_bytes of dynamic LDS (the scene copy)
+  int ring;      // LDS stack ring depth per lane; deeper entries go to the overflow area
+};
+constexpr TraceInfo kTrace[kTraceVariants] = {
+    {k_trace_closest, 1, false, kStackLdsC},
+    {k_trace_shadow, 1, false, kStackLds},
+    {k_trace_shadow_split, 1, false, kStackLds},
+    {k_trace_closest_big, 1, false, kStackLdsC},
+    {k_trace_shadow_big, 1, false, kStackLds},
+    {k_trace_shadow_uni, 1, false, kStackLds},
+    {k_trace_shadow_big_uni, 1, false, kStackLds},
+    {k_trace_closest_small, YK_SMALL_W, true, YK_SMALL_RING},
+    {k_trace_shadow_small, YK_SMALL_W, true, YK_SMALL_RING},
+    {k_trace_shadow_small_split, YK_SMALL_W, true, YK_SMALL_RING},
+    {k_trace_shadow_uni_small, YK_SMALL_W, true, YK_SMALL_RING},
+};
+
 struct yk_device {
   int ordinal = 0;
   int cus = 0;
-  int per_cu[2] = {1, 1};  // resident trace waves per CU: [0] any-hit, [1] closest
-  int per_cu_big[2] = {1, 1};  // the same for the BIG-leaf kernels
+  int per_cu[kTraceVariants] = {};  // resident workgroups per CU of each trace kernel (fill_trace_occupancy)
   // small scenes: traversal data copied to LDS per workgroup (install_traversal)
   bool small = false;
   size_t small_bytes = 0;
-  int per_cu_split[2] = {1, 1};  // the split-slot any-hit kernels: waves (large trees), workgroups (small scenes)
-  int per_cu_small[3] = {1, 1, 1};  // resident workgroups (YK_SMALL_W waves) per CU: any-hit, closest, universal any-hit
   hipStream_t stream = nullptr;  // = pipe[0].stream (ray queries, film resolve)
   bool uploaded = false;
   const yk_scene* uploaded_scene = nullptr;  // the scene the resident arrays came from
@@ -4138,7 +4174,7 @@ struct yk_device {
   // own xGMI link)
   DBuf<float> mfilm, macc;
   DBuf<float> mstage[kMaxMultiDev];
-  // render_pass's tile lists (grow-only, so repeated renders allocate nothing)
+  // the frame plan's tile lists (upload_frame_plan; grow-only, so repeated renders allocate nothing)
   DBuf<int4> tiles_dev;
   DBuf<int> base_dev, pix_dev, pmap_dev, rank_dev;
   DBuf<uint8_t> flags_dev;
@@ -4559,28 +4595,47 @@ inline RaySrc shadow_src(const Batch& B) {
                 (unsigned)B.kstride};
 }
 
+// The kernel a trace runs: small scenes (not with big leaves) the LDS-copy
+// kernels, big-leaf trees the BIG ones, universal scenes their own any-hit
+// kernels; split: a render batch's shadow slots in the split form (never
+// universal or big-leaf: shadow_split).
+TraceVariant trace_variant(const yk_device* d, bool closest, bool split) {
+  const bool small = d->small && !d->big_leaves;
+  if (split) return small ? kShadowSmallSplit : kShadowSplit;
+  if (small) return closest ? kClosestSmall : d->S.uni ? kShadowUniSmall : kShadowSmall;
+  if (closest) return d->big_leaves ? kClosestBig : kClosest;
+  if (d->S.uni) return d->big_leaves ? kShadowBigUni : kShadowUni;
+  return d->big_leaves ? kShadowBig : kShadow;
+}
+
+// per_cu of the variants with / without dynamic LDS (install_traversal once
+// small_bytes is known / yk_device_open)
+void fill_trace_occupancy(yk_device* d, bool dyn_lds) {
+  for (int v = 0; v < kTraceVariants; ++v) {
+    const TraceInfo& t = kTrace[v];
+    if (t.dyn_lds != dyn_lds) continue;
+    int blocks = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, t.kernel, 64 * t.waves,
+                                                        dyn_lds ? d->small_bytes : 0));
+    d->per_cu[v] = std::max(1, blocks);
+  }
+  if (dyn_lds) return;
+  // on large trees the universal any-hit kernels run on the plain ones' grids
+  d->per_cu[kShadowUni] = d->per_cu[kShadow];
+  d->per_cu[kShadowBigUni] = d->per_cu[kShadowBig];
+}
+
 template <bool CLOSEST>
 void enqueue_trace(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits,
                    uint8_t* occ, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0, hipEvent_t ev1) {
-  const bool small = d->small && !d->big_leaves;
-  const int waves = small ? YK_SMALL_W : 1;  // per workgroup
-  const bool split = !CLOSEST && rays.rays == nullptr;  // render batches with split slots (never uni / big)
-  const long long per_cu = split ? d->per_cu_split[small ? 1 : 0]
-                           : small ? d->per_cu_small[(!CLOSEST && d->S.uni) ? 2 : (int)CLOSEST]
-                           : d->big_leaves ? d->per_cu_big[CLOSEST]
-                                           : d->per_cu[CLOSEST];
-  const long long grid = (long long)d->cus * per_cu;
-  const int ovf_depth = std::max(1, stack_depth(d) - (small ? YK_SMALL_RING : (CLOSEST ? kStackLdsC : kStackLds)));
-  P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64 * waves);
+  const TraceVariant v = trace_variant(d, CLOSEST, !CLOSEST && rays.rays == nullptr);
+  const TraceInfo& t = kTrace[v];
+  const long long grid = (long long)d->cus * d->per_cu[v];
+  const int ovf_depth = std::max(1, stack_depth(d) - t.ring);
+  P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64 * t.waves);
   if (ev0) HIPCHK(hipEventRecord(ev0, P.stream));
-  auto kern = split ? (small ? k_trace_shadow_small_split : k_trace_shadow_split)
-              : small ? (CLOSEST ? k_trace_closest_small : d->S.uni ? k_trace_shadow_uni_small : k_trace_shadow_small)
-              : CLOSEST ? (d->big_leaves ? k_trace_closest_big : k_trace_closest)
-                        : (d->S.uni ? (d->big_leaves ? k_trace_shadow_big_uni : k_trace_shadow_uni)
-                                    : (d->big_leaves ? k_trace_shadow_big : k_trace_shadow));
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), small ? d->small_bytes : 0, P.stream, d->S, rays,
-                     idx, n, hits, occ, work, acc, P.ovf.p, ovf_depth, CLOSEST ? d->refill : d->refill_shadow);
-  HIPCHK(hipGetLastError());
+  launch(t.kernel, (unsigned)grid, 64 * t.waves, t.dyn_lds ? d->small_bytes : 0, P.stream, d->S, rays, idx, n, hits,
+         occ, work, acc, P.ovf.p, ovf_depth, CLOSEST ? d->refill : d->refill_shadow);
   if (ev1) HIPCHK(hipEventRecord(ev1, P.stream));
 }
 
@@ -4592,9 +4647,8 @@ void enqueue_trace_ts(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, R
   const int ovf_depth = std::max(1, stack_depth(d) - kStackLds);
   P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64);
   if (ev0) HIPCHK(hipEventRecord(ev0, P.stream));
-  hipLaunchKernelGGL(k_trace_shadow_ts, dim3((unsigned)grid), dim3(64), 0, P.stream, d->S, rays, idx, n, occ, filt,
-                     max_depth, work, acc, P.ovf.p, ovf_depth, d->refill_shadow);
-  HIPCHK(hipGetLastError());
+  launch(k_trace_shadow_ts, (unsigned)grid, 64, 0, P.stream, d->S, rays, idx, n, occ, filt, max_depth, work, acc,
+         P.ovf.p, ovf_depth, d->refill_shadow);
   if (ev1) HIPCHK(hipEventRecord(ev1, P.stream));
 }
 
@@ -4620,9 +4674,29 @@ bool shadow_split(const yk_device* d, const yk_render_params* p) {
   return (e ? std::atoi(e) != 0 : K >= 4) && !d->S.uni && !d->big_leaves && !p->transp_shadows;
 }
 
+// One kernel kind's share of yk_stats.
+void add_trace_stats(yk_stats* st, bool closest, uint64_t rays, uint64_t nodes, uint64_t tris, double ms,
+                     uint64_t launches = 1) {
+  if (closest) {
+    st->closest_rays += rays;
+    st->closest_nodes += nodes;
+    st->closest_tris += tris;
+    st->ms_closest += ms;
+    st->closest_launches += launches;
+  } else {
+    st->shadow_rays += rays;
+    st->shadow_nodes += nodes;
+    st->shadow_tris += tris;
+    st->ms_shadow += ms;
+    st->shadow_launches += launches;
+  }
+}
+
 // Ray-query entry points: one launch, synchronised, statistics added to st.
+// filt: the transparent-shadow query (k_trace_shadow_ts, up to ts_depth surfaces).
 template <bool CLOSEST>
-void launch_trace(yk_device* d, Pipe& P, const yk_ray* rays, long long n, yk_hit* hits, uint8_t* occ, yk_stats* st) {
+void launch_trace(yk_device* d, Pipe& P, const yk_ray* rays, long long n, yk_hit* hits, uint8_t* occ, yk_stats* st,
+                  float* filt = nullptr, int ts_depth = 0) {
   if (n <= 0) return;
   if (n > 0x7FFFFFFFll - (1ll << 24)) throw std::invalid_argument("ray batch too large (max ~2^31 rays per call)");
   unsigned long long* work = P.counters.p;
@@ -4634,7 +4708,9 @@ void launch_trace(yk_device* d, Pipe& P, const yk_ray* rays, long long n, yk_hit
     HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_spill_stores), &z, sizeof z, 0, hipMemcpyHostToDevice, P.stream));
   }
 #endif
-  enqueue_trace<CLOSEST>(d, P, ray_src(rays), nullptr, RayCount{nullptr, 0, n}, hits, occ, work, acc, P.ev0, P.ev1);
+  const RayCount cnt{nullptr, 0, n};
+  if (filt) enqueue_trace_ts(d, P, ray_src(rays), nullptr, cnt, occ, filt, ts_depth, work, acc, P.ev0, P.ev1);
+  else enqueue_trace<CLOSEST>(d, P, ray_src(rays), nullptr, cnt, hits, occ, work, acc, P.ev0, P.ev1);
   unsigned long long h[13];
   HIPCHK(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, P.stream));
   HIPCHK(hipStreamSynchronize(P.stream));
@@ -4659,20 +4735,7 @@ void launch_trace(yk_device* d, Pipe& P, const yk_ray* rays, long long n, yk_hit
                  CLOSEST ? "closest" : "shadow", sp, (double)sp / (double)n, 8e-6 * (double)sp);
   }
 #endif
-  if (!st) return;
-  if (CLOSEST) {
-    st->closest_rays += (uint64_t)n;
-    st->closest_nodes += h[0];
-    st->closest_tris += h[1];
-    st->ms_closest += ms;
-    st->closest_launches++;
-  } else {
-    st->shadow_rays += (uint64_t)n;
-    st->shadow_nodes += h[0];
-    st->shadow_tris += h[1];
-    st->ms_shadow += ms;
-    st->shadow_launches++;
-  }
+  if (st) add_trace_stats(st, CLOSEST, (uint64_t)n, h[0], h[1], ms);
 }
 
 inline unsigned grid_for(long long n, int b = 256) { return (unsigned)((n + b - 1) / b); }
@@ -4721,9 +4784,7 @@ void set_handout(yk_device* d, size_t nn) {
 
 // Node packets of the resident tree (k_pack_nodes).
 void pack_nodes(yk_device* d, size_t nn) {
-  hipLaunchKernelGGL(k_pack_nodes, dim3(grid_for((long long)nn)), dim3(256), 0, d->stream, d->nodes.p, d->pk.p,
-                     (unsigned)nn);
-  HIPCHK(hipGetLastError());
+  launch(k_pack_nodes, grid_for((long long)nn), 256, 0, d->stream, d->nodes.p, d->pk.p, (unsigned)nn);
   d->S.pk = d->pk.p;
 }
 
@@ -4735,9 +4796,8 @@ void install_traversal(yk_device* d, size_t nn, size_t nleaf, uint32_t max_leaf_
   HIPCHK(hipDeviceSynchronize());  // every copy into nodes / leaf / tris has landed
   if (nleaf) {
     d->ltris.ensure(kTriWords * nleaf + kRecPad);
-    hipLaunchKernelGGL(k_gather_leaf_tris, dim3(grid_for((long long)nleaf)), dim3(256), 0, d->stream, d->tris.p,
-                       d->leaf.p, d->ltris.p, (unsigned)nleaf);
-    HIPCHK(hipGetLastError());
+    launch(k_gather_leaf_tris, grid_for((long long)nleaf), 256, 0, d->stream, d->tris.p, d->leaf.p, d->ltris.p,
+           (unsigned)nleaf);
   }
   d->S.ltris = nleaf ? d->ltris.p : nullptr;
   d->S.nlref = (unsigned)nleaf;
@@ -4753,21 +4813,7 @@ void install_traversal(yk_device* d, size_t nn, size_t nleaf, uint32_t max_leaf_
   const size_t small_max = small_v > 1 ? (size_t)std::min(small_v, 47104ll) : (size_t)YK_SMALL_MAX;
   d->small_bytes = small_scene_bytes(nn, d->S.ntris, nleaf);
   d->small = small_v != 0 && d->small_bytes <= small_max;
-  if (d->small) {
-    int blocks = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_small, 64 * YK_SMALL_W,
-                                                        d->small_bytes));
-    d->per_cu_small[0] = std::max(1, blocks);
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_closest_small, 64 * YK_SMALL_W,
-                                                        d->small_bytes));
-    d->per_cu_small[1] = std::max(1, blocks);
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_uni_small, 64 * YK_SMALL_W,
-                                                        d->small_bytes));
-    d->per_cu_small[2] = std::max(1, blocks);
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_small_split, 64 * YK_SMALL_W,
-                                                        d->small_bytes));
-    d->per_cu_split[1] = std::max(1, blocks);
-  }
+  if (d->small) fill_trace_occupancy(d, true);
 }
 
 }  // namespace
@@ -4791,25 +4837,17 @@ int yk_device_open(int32_t ordinal, yk_device** out) {
   for (auto& P : d->pipe) P.create();
   for (auto& e : d->gather_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   d->stream = d->pipe[0].stream;
+  std::fill(d->per_cu, d->per_cu + kTraceVariants, 1);
+  fill_trace_occupancy(d, false);
   int blocks = 0;
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow, 64, 0));
-  d->per_cu[0] = std::max(1, blocks);
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_split, 64, 0));
-  d->per_cu_split[0] = std::max(1, blocks);
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_closest, 64, 0));
-  d->per_cu[1] = std::max(1, blocks);
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_big, 64, 0));
-  d->per_cu_big[0] = std::max(1, blocks);
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_closest_big, 64, 0));
-  d->per_cu_big[1] = std::max(1, blocks);
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_ts, 64, 0));
   d->per_cu_ts = std::max(1, blocks);
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_pm_lookup<false>, 64, 0));
   d->per_cu_lookup[0] = std::max(1, blocks);
   if (const char* v = std::getenv("YK_VERBOSE"); v && std::atoi(v) > 0)
     std::fprintf(stderr, "[libyk] %d CUs; resident workgroups per CU: any-hit %d, closest %d, big %d / %d, "
-                 "transparent-shadow %d\n", d->cus, d->per_cu[0], d->per_cu[1], d->per_cu_big[0], d->per_cu_big[1],
-                 d->per_cu_ts);
+                 "transparent-shadow %d\n", d->cus, d->per_cu[kShadow], d->per_cu[kClosest], d->per_cu[kShadowBig],
+                 d->per_cu[kClosestBig], d->per_cu_ts);
   upload_qmc();
   *out = d;
   return YK_OK;
@@ -5017,29 +5055,10 @@ int yk_trace_shadow_filtered(yk_device* d, const yk_ray* d_rays, int64_t n, uint
   if (max_depth < 0 || max_depth > 8) return set_error(YK_ERR_UNSUPPORTED, "max_depth must be in [0, 8]");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_trace_shadow_filtered: no scene uploaded");
   if (n <= 0) return YK_OK;
-  if (n > 0x7FFFFFFFll - (1ll << 24)) return set_error(YK_ERR_ARG, "ray batch too large");
   YK_GUARD_BEGIN
   HIPCHK(hipSetDevice(d->ordinal));
   bind_constants(d);  // the transparent-shadow leaf body reads the materials
-  Pipe& P = d->pipe[0];
-  unsigned long long* work = P.counters.p;
-  unsigned long long* acc = P.counters.p + 128;
-  HIPCHK(hipMemsetAsync(work, 0, 136 * sizeof(unsigned long long), P.stream));
-  enqueue_trace_ts(d, P, ray_src(d_rays), nullptr, RayCount{nullptr, 0, n}, d_occ, d_filter, max_depth,
-                   work, acc, P.ev0, P.ev1);
-  unsigned long long h[4];
-  HIPCHK(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, P.stream));
-  HIPCHK(hipStreamSynchronize(P.stream));
-  if (h[2]) return set_error(YK_ERR_INTERNAL, "kd-tree traversal watchdog fired");
-  if (st) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, P.ev0, P.ev1));
-    st->shadow_rays += (uint64_t)n;
-    st->shadow_nodes += h[0];
-    st->shadow_tris += h[1];
-    st->ms_shadow += ms;
-    st->shadow_launches++;
-  }
+  launch_trace<false>(d, d->pipe[0], d_rays, n, nullptr, d_occ, st, d_filter, max_depth);
   return YK_OK;
   YK_GUARD_END
 }
@@ -5148,829 +5167,4 @@ int yk_film_filter_from_table(const float* table, float filterw, yk_render_param
 #include "yk_kdtree_gpu.inc"
 #include "yk_test_hooks.inc"
 
-// One renderPass (integrator.cc:172-224): n samples per pixel from pixel
-// sample `off`; flags (film-local bytes, host) restricts it to the pixels
-// imageFilm_t::nextPass flagged.
-struct PassSpec {
-  int n, off;
-  bool multipass;
-  const uint8_t* flags;
-};
-
-static int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, float* d_film,
-                       yk_stats* st, const PassSpec& ps) {
-  if (!d || !p || !d_film || nshards < 1 || shard < 0 || shard >= nshards)
-    return set_error(YK_ERR_ARG, "yk_render_shard: bad arguments");
-  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_render_shard: no scene uploaded");
-  if (p->filter < YK_FILTER_BOX || p->filter > YK_FILTER_LANCZOS) return set_error(YK_ERR_ARG, "unknown filter");
-  if (p->integrator != YK_INTEGRATOR_PATH && p->integrator != YK_INTEGRATOR_DIRECT &&
-      p->integrator != YK_INTEGRATOR_PHOTON)
-    return set_error(YK_ERR_ARG, "unknown integrator");
-  const bool pm = p->integrator == YK_INTEGRATOR_PHOTON;
-  if (p->integrator == YK_INTEGRATOR_PATH &&
-      (p->caustic_type < YK_CAUSTIC_NONE || p->caustic_type > YK_CAUSTIC_BOTH))
-    return set_error(YK_ERR_ARG, "unknown caustic_type");
-  // pathtracing with photon caustics reads the caustic map its preprocess built
-  const bool pt_cmap = p->integrator == YK_INTEGRATOR_PATH &&
-                       (p->caustic_type == YK_CAUSTIC_PHOTON || p->caustic_type == YK_CAUSTIC_BOTH);
-  // direct lighting's own options (directlight.cc:137-142): photon caustics
-  // under pathtracing's rules, ambient occlusion with its own shadow slots
-  const bool direct = p->integrator == YK_INTEGRATOR_DIRECT;
-  const bool dl_cmap = direct && p->dl_caustics != 0;
-  const bool cmap = pt_cmap || dl_cmap;
-  const bool ao = direct && p->do_ao != 0;
-  if ((pm || cmap) && (!d->pm_ready || d->pm_integrator != p->integrator))
-    return set_error(YK_ERR_STATE, "photon maps: call yk_photon_build for this integrator first (preprocess)");
-  if ((pm || cmap) && std::memcmp(&p->photon, &d->pm_params, sizeof(yk_photon_params)) != 0)
-    return set_error(YK_ERR_STATE, "photon mapping: the maps were built with different photon parameters");
-  if (ao && p->ao_samples < 1) return set_error(YK_ERR_ARG, "AO_samples must be >= 1");
-  if (ao && !(std::isfinite(p->ao_distance) && p->ao_distance > 0.f))
-    return set_error(YK_ERR_ARG, "AO_distance must be finite and > 0");
-  if (ao && (long long)d->sum_light_slots + p->ao_samples > 8192)
-    return set_error(YK_ERR_UNSUPPORTED, "too many shadow slots per shading point (light samples + AO_samples > 8192)");
-  if (p->integrator == YK_INTEGRATOR_PATH && (p->bounces < 1 || 4 * p->bounces + 4 >= 50))
-    return set_error(YK_ERR_UNSUPPORTED, "bounces must be in [1, 11]");
-  if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
-  if (p->filter_width != 0.f && !(p->filter_width >= 0.501f && p->filter_width <= 4.f))
-    return set_error(YK_ERR_ARG, "filter_width must be 0 or in [0.501, 4]");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  bind_constants(d);
-  auto t0 = std::chrono::steady_clock::now();
-  FilmConst F = make_film(p);
-  if (F.tile > 4096) return set_error(YK_ERR_UNSUPPORTED, "tile_size > 4096");
-  F.shard = shard;
-  F.nshards = nshards;
-  F.spp = ps.n;
-  F.d1 = (float)(1.0 / (double)(float)ps.n);
-  const int spp = F.spp;
-  const int nty = (p->height + F.tile - 1) / F.tile;
-  const int ntiles = F.ntx * nty;
-  if (ntiles >= (1 << 19)) return set_error(YK_ERR_UNSUPPORTED, "too many tiles");
-  std::vector<int> owned;  // the shard's tiles in the order the film hands them out
-  std::vector<int> rank_of;  // custom order: tile -> rank in `owned`, -1 other shards' tiles
-  if (p->tile_order && p->tile_order_len > 0) {
-    if (p->tile_order_len != ntiles)
-      return set_error(YK_ERR_ARG, "tile_order must list every tile of the render area once");
-    rank_of.assign((size_t)ntiles, -1);
-    std::vector<char> seen((size_t)ntiles, 0);
-    for (int i = 0; i < ntiles; ++i) {
-      const int t = p->tile_order[i];
-      if (t < 0 || t >= ntiles || seen[(size_t)t]) return set_error(YK_ERR_ARG, "tile_order is not a permutation of the tiles");
-      seen[(size_t)t] = 1;
-      if (t % nshards == shard) {
-        rank_of[(size_t)t] = (int)owned.size();
-        owned.push_back(t);
-      }
-    }
-  } else {
-    for (int t = shard; t < ntiles; t += nshards) owned.push_back(t);
-  }
-  bool aborted = false;
-  RenderConst R{};
-  R.spp = spp;
-  R.nsub = p->integrator == YK_INTEGRATOR_PATH ? std::max(1, p->path_samples) : 1;
-  R.pm_fg = (pm && p->photon.final_gather && !p->photon.show_map) ? 1 : 0;
-  R.pm_showmap = (pm && p->photon.show_map) ? 1 : 0;
-  // transparent shadows: the device keeps the filtered-prim set of a shadow
-  // ray in 9 registers, so at most 8 transparent surfaces (defaults 4-5)
-  if (p->transp_shadows && (p->shadow_depth < 0 || p->shadow_depth > 8))
-    return set_error(YK_ERR_UNSUPPORTED, "shadowDepth must be in [0, 8] with transpShad");
-  if (R.pm_fg) R.nsub = std::max(1, p->photon.fg_samples);  // nSampl = max(1, nPaths / rayDivision)
-  const PMConst PMC = (pm || cmap) ? pm_const(d, p->photon) : PMConst{};
-  R.bounces = p->bounces;
-  R.integrator = p->integrator;
-  R.transp_bg = p->transp_background;
-  R.nlights = d->nlights;
-  R.has_bg = d->has_bg ? 1 : 0;
-  for (int k = 0; k < 3; ++k) R.bg[k] = d->bg[k];
-  R.d1 = F.d1;
-  R.spec = d->spec ? 1 : 0;
-  R.trace_caustics = (p->integrator == YK_INTEGRATOR_PATH &&
-                      (p->caustic_type == YK_CAUSTIC_PATH || p->caustic_type == YK_CAUSTIC_BOTH)) ? 1 : 0;
-  R.rdepth = p->raydepth;
-  R.level = 0;
-  R.multipass = ps.multipass ? 1 : 0;
-  R.pass_off = ps.off;
-  R.ps = (R.spec || R.multipass) ? 1 : 0;
-  // the lights' slots, then the AO rays' (gen_ao)
-  const int K = std::max(1, d->sum_light_slots + ao_slots(p));
-  AOConst AOC{};
-  if (ao) {
-    AOC.n = p->ao_samples;
-    AOC.k0 = d->sum_light_slots;
-    AOC.dist = p->ao_distance;
-    for (int k = 0; k < 3; ++k) AOC.col[k] = p->ao_color[k];
-  }
-  // specular recursion: the node store holds min(raydepth, 19) levels (plan_batches)
-  const int spec_levels = d->spec ? std::max(0, std::min(p->raydepth, 19)) : 0;
-  const long long spec_worst = (2ll << spec_levels) - 1;
-  // merged shadow launch (k_resolve_merged): path tracing without specular
-  // recursion, photon maps or transparent shadows, one sub-path; YK_MERGE=0
-  // (read per render: A/B runs, tests) keeps one any-hit launch per bounce
-  const bool merged = [&] {
-    const char* e = std::getenv("YK_MERGE");
-    return !(e && std::atoi(e) == 0) && p->integrator == YK_INTEGRATOR_PATH && !d->spec && !pt_cmap &&
-           !p->transp_shadows && p->path_samples <= 1 && p->bounces >= 1;
-  }();
-  R.merged = merged ? 1 : 0;
-  // HBM for the batch buffers of all pipes (YK_BATCH_GB, default 64 of the
-  // 288 GB, 192 with the merged launch's slot regions: C2's eight slots per
-  // sample in five regions at 128 GB cut its batches from 16M to 12.6M
-  // samples, six batches on four pipes, -5 %; at 192 GB it keeps four)
-  static const long long batch_gb_env = [] {
-    const char* e = std::getenv("YK_BATCH_GB");
-    const long long v = e ? std::atoll(e) : 0;
-    return (v > 0 && v <= 240) ? v : 0ll;
-  }();
-  const bool split = shadow_split(d, p);
-  // batches, pipes and every buffer size: plan_batches. YK_BATCH_SAMPLES and
-  // YK_PIPES are read on every render (A/B runs, tests)
-  yk_batch_plan_in pin{};
-  pin.slots = K;
-  pin.bounces = merged ? p->bounces : 0;
-  pin.merged = merged ? 1 : 0;
-  pin.split = split ? 1 : 0;
-  pin.transp_shadows = p->transp_shadows ? 1 : 0;
-  pin.spec = d->spec ? 1 : 0;
-  pin.final_gather = R.pm_fg;
-  pin.spec_levels = spec_levels;
-  pin.tile = F.tile;
-  pin.spp = spp;
-  pin.pipes = pipes_env();
-  pin.owned_tiles = (long long)owned.size();
-  {
-    const char* e = std::getenv("YK_BATCH_SAMPLES");
-    pin.target_samples = e ? std::atoll(e) : 0;
-  }
-  pin.budget_bytes = (batch_gb_env ? batch_gb_env : (merged ? 192ll : 64ll)) << 30;
-  yk_batch_plan plan;
-  if (const char* why = plan_batches(pin, plan)) return set_error(YK_ERR_UNSUPPORTED, why);
-  const int regions = plan.regions;
-  const int tiles_per_batch = plan.tiles_per_batch;
-  const long long maxc = plan.maxc;
-  const int nbatch = plan.nbatch;
-  const int npipes = plan.npipes;
-  d->last_plan = plan;
-  d->last_plan_valid = true;
-  d->last_max_batches = (nbatch + npipes - 1) / npipes;
-  const bool path = p->integrator == YK_INTEGRATOR_PATH;
-  // final gathering: hits 0..fg_bounces of each gather path, queue words up to fg_bounces + 1
-  const int bounces = path ? R.bounces : (R.pm_fg ? p->photon.fg_bounces + 1 : 0);
-  const int nsub = (path || R.pm_fg) ? R.nsub : 1;
-
-  // ---- tile lists of all batches, uploaded once
-  std::vector<int4> tiles_all;
-  std::vector<int> base_all((size_t)nbatch * (tiles_per_batch + 1), 0);
-  std::vector<long long> nc_of(nbatch);
-  std::vector<int4> rect_of(nbatch);
-  // adaptive pass: flagged pixels per batch (tile order, rows, columns) and
-  // the film-pixel -> batch-local first sample map the gather reads
-  std::vector<int> pix_all;
-  std::vector<size_t> pix_off(nbatch, 0);
-  std::vector<int> pmap;
-  if (ps.flags) {
-    if (F.cx1 > 65535 || F.cy1 > 65535) return set_error(YK_ERR_UNSUPPORTED, "adaptive passes need coordinates < 65536");
-    pmap.assign((size_t)F.w * F.h, -1);
-  }
-  for (int bi = 0; bi < nbatch; ++bi) {
-    const size_t tb0 = (size_t)bi * tiles_per_batch, tb1 = std::min(owned.size(), tb0 + (size_t)tiles_per_batch);
-    long long nc = 0;
-    int rx0 = 1 << 30, ry0 = 1 << 30, rx1 = -(1 << 30), ry1 = -(1 << 30);
-    pix_off[bi] = pix_all.size();
-    for (size_t k = tb0; k < tb1; ++k) {
-      const int t = owned[k];
-      const int X = F.cx0 + (t % F.ntx) * F.tile, Y = F.cy0 + (t / F.ntx) * F.tile;
-      const int W = std::min(F.tile, F.cx1 - X), H = std::min(F.tile, F.cy1 - Y);
-      tiles_all.push_back(make_int4(X, Y, W, H));
-      base_all[(size_t)bi * (tiles_per_batch + 1) + (k - tb0)] = (int)nc;
-      if (ps.flags) {
-        for (int yy = Y; yy < Y + H; ++yy)
-          for (int xx = X; xx < X + W; ++xx) {
-            const size_t fp = (size_t)(yy - F.cy0) * F.w + (xx - F.cx0);
-            if (!ps.flags[fp]) continue;
-            pmap[fp] = (int)nc;
-            pix_all.push_back((yy << 16) | xx);
-            nc += spp;
-          }
-      } else {
-        nc += (long long)W * H * spp;
-      }
-      rx0 = std::min(rx0, X);
-      ry0 = std::min(ry0, Y);
-      rx1 = std::max(rx1, X + W);
-      ry1 = std::max(ry1, Y + H);
-    }
-    base_all[(size_t)bi * (tiles_per_batch + 1) + (tb1 - tb0)] = (int)nc;
-    nc_of[bi] = nc;
-    rect_of[bi] = make_int4(rx0, ry0, rx1, ry1);
-  }
-  // tile lists, adaptive-pass pixel lists and flags live on the handle
-  // (grow-only): a repeated render allocates nothing
-  DBuf<int4>& tiles_dev = d->tiles_dev;
-  DBuf<int>& base_dev = d->base_dev;
-  tiles_dev.ensure(tiles_all.size());
-  base_dev.ensure(base_all.size());
-  HIPCHK(hipMemcpy(tiles_dev.p, tiles_all.data(), tiles_all.size() * sizeof(int4), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(base_dev.p, base_all.data(), base_all.size() * sizeof(int), hipMemcpyHostToDevice));
-  DBuf<int>& pix_dev = d->pix_dev;
-  DBuf<int>& pmap_dev = d->pmap_dev;
-  if (ps.flags) {
-    pix_dev.ensure(std::max<size_t>(1, pix_all.size()));
-    pmap_dev.ensure(pmap.size());
-    if (!pix_all.empty())
-      HIPCHK(hipMemcpy(pix_dev.p, pix_all.data(), pix_all.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(pmap_dev.p, pmap.data(), pmap.size() * sizeof(int), hipMemcpyHostToDevice));
-  }
-  F.rank_of = nullptr;
-  if (!rank_of.empty()) {  // custom tile order: the film gather walks a window's tiles by rank
-    d->rank_dev.ensure(rank_of.size());
-    HIPCHK(hipMemcpy(d->rank_dev.p, rank_of.data(), rank_of.size() * sizeof(int), hipMemcpyHostToDevice));
-    F.rank_of = d->rank_dev.p;
-  }
-
-  // ---- per-pipe device words: [0, 2 kAccWords) accumulators {closest
-  // nodes, tris, errors, rays; any-hit ...}; then per batch: queue-count words
-  // (isub, depth), the final gather's lookup-queue counts (isub, depth) and
-  // one 128-word hand-out block per trace or lookup launch.
-  // All zeroed once; no launch needs a reset or a host round trip.
-  const int qwords_per_batch = nsub * (bounces + 1);
-  const int launches_per_batch = 2 + 2 * nsub * bounces + (R.pm_fg ? nsub * bounces : 0);
-  const long long words_per_batch = 2ll * qwords_per_batch + 128ll * launches_per_batch;
-  Batch Bp[kPipes];
-  for (int pi = 0; pi < npipes; ++pi) {
-    Pipe& P = d->pipe[pi];
-    const int nb_here = (nbatch - pi + npipes - 1) / npipes;
-    P.words.ensure((size_t)(2 * kAccWords + (d->spec ? 0 : words_per_batch * nb_here)));
-    HIPCHK(hipMemsetAsync(P.words.p, 0, P.words.n * sizeof(unsigned long long), P.stream));
-    Bp[pi] = P.bind(maxc, K, tiles_per_batch, R.ps != 0, p->transp_shadows != 0, regions, split);
-    if (R.pm_fg) {
-      P.fgl.ensure(3 * maxc);
-      P.fglen.ensure(maxc);
-      P.lkq.ensure(2 * maxc);
-    }
-  }
-  NodeStore NS{};
-  if (d->spec) {
-    const long long cap = maxc * spec_worst;
-    d->nE.ensure(3 * cap);
-    d->nD.ensure(3 * cap);
-    d->nP.ensure(3 * cap);
-    d->nrcol.ensure(6 * cap);
-    d->nalpha.ensure(maxc);
-    d->nflags.ensure(cap);
-    d->nchild.ensure(2 * cap);
-    d->nray.ensure(cap);
-    d->nsoffs.ensure(cap);
-    d->npsample.ensure(cap);
-    d->ncount.ensure(1);
-    d->noverflow.ensure(1);
-    d->nmalpha.ensure(cap);
-    d->spec_words.ensure((size_t)words_per_batch);
-    NS = NodeStore{d->nE.p,   d->nD.p,     d->nP.p,       d->nflags.p, d->nchild.p,  d->nrcol.p,    d->nalpha.p,
-                   d->nray.p, d->nsoffs.p, d->npsample.p, d->ncount.p, (long long)cap, d->noverflow.p,
-                   d->nmalpha.p};
-    HIPCHK(hipMemsetAsync(d->noverflow.p, 0, sizeof(int), d->pipe[0].stream));
-  }
-  struct Timed {
-    int pipe;
-    size_t ev;
-    bool closest;
-  };
-  std::vector<Timed> timed;
-  size_t evn[kPipes] = {};
-  long long samples_total = 0;
-
-  for (int bi = 0; bi < nbatch; ++bi) {
-    const int pi = bi % npipes;
-    Pipe& P = d->pipe[pi];
-    const Batch& B = Bp[pi];
-    if (d->abort_fn) {
-      // abort polling between batches: this pipe's previous batch has
-      // finished (the other pipes keep the GPU busy meanwhile)
-      if (bi >= npipes) HIPCHK(hipStreamSynchronize(P.stream));
-      if (d->abort_fn(d->abort_user)) {
-        aborted = true;
-        break;
-      }
-    }
-    const long long nc = nc_of[bi];
-    unsigned long long* bw = d->spec ? d->spec_words.p : P.words.p + 2 * kAccWords + words_per_batch * (bi / npipes);
-    auto qw = [&](int isub, int depth) { return bw + isub * (bounces + 1) + depth; };
-    int launch = 0;
-    auto trace = [&](bool closest, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits,
-                     uint8_t* occ) {
-      unsigned long long* work = bw + 2ll * qwords_per_batch + 128ll * launch++;
-      const hipEvent_t e0 = P.event(evn[pi]), e1 = P.event(evn[pi] + 1);
-      timed.push_back(Timed{pi, evn[pi], closest});
-      evn[pi] += 2;
-      if (closest) enqueue_trace<true>(d, P, rays, idx, n, hits, occ, work, P.words.p, e0, e1);
-      else if (B.ts)  // transparent shadows: IntersectTS, filter colour into the slot
-        enqueue_trace_ts(d, P, rays, idx, n, occ, B.s_filt, p->shadow_depth, work, P.words.p + kAccWords, e0, e1);
-      else enqueue_trace<false>(d, P, rays, idx, n, hits, occ, work, P.words.p + kAccWords, e0, e1);
-    };
-    // photonIntegrator_t::integrate after the direct light: show_map /
-    // diffuse-map estimate, final gathering, caustics (photonintegr.cc:819-852)
-    auto pm_entries = [&](const Batch& Bc, const RenderConst& Rc, long long n) {
-      if (pm && (PMC.show_map || !PMC.final_gather)) {
-        hipLaunchKernelGGL(k_pm_post, dim3(grid_for(n, 64)), dim3(64), 0, P.stream, d->S, Bc, PMC, n);
-        HIPCHK(hipGetLastError());
-      }
-      // final gathering (photonintegr.cc:637-790): gather path index outermost,
-      // pathCol accumulated across paths in the reference's order
-      for (int isub = 0; isub < (R.pm_fg ? nsub : 0); ++isub) {
-        hipLaunchKernelGGL(d->diff_only ? k_fg_start<true> : k_fg_start<false>, dim3(grid_for(n, YK_APPEND_BLOCK)), dim3(YK_APPEND_BLOCK), 0, P.stream, d->S, Bc, Rc, n, isub, P.fgl.p,
-                           qw(isub, 0));
-        HIPCHK(hipGetLastError());
-        int qin = 1;
-        for (int it = 0; it <= p->photon.fg_bounces; ++it) {
-          const unsigned long long* in_w = qw(isub, it);
-          unsigned long long* out_w = qw(isub, it + 1);
-          trace(true, ray_src(Bc.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, Bc.q_hits[qin], nullptr);
-          unsigned long long* lk_w = qw(isub, it) + qwords_per_batch;  // lookup-queue count
-          hipLaunchKernelGGL(d->diff_only ? k_fg_hit<true> : k_fg_hit<false>, dim3(grid_for(n, YK_APPEND_BLOCK)), dim3(YK_APPEND_BLOCK), 0,
-                             P.stream, d->S, Bc, Rc, PMC, in_w, it, isub, qin,
-                             P.fgl.p, P.fglen.p, out_w, P.lkq.p, lk_w);
-          HIPCHK(hipGetLastError());
-          if (it < p->photon.fg_bounces) trace(false, shadow_src(Bc), Bc.s_idx, RayCount{out_w, 0, 0}, nullptr, Bc.s_occl);
-          {
-            const bool lds = lookup_lds(d);
-            unsigned long long* work = bw + 2ll * qwords_per_batch + 128ll * launch++;
-            hipLaunchKernelGGL(lds ? k_pm_lookup<true> : k_pm_lookup<false>,
-                               dim3((unsigned)((long long)d->cus * d->per_cu_lookup[lds ? 1 : 0])), dim3(64),
-                               lds ? lookup_lds_bytes(d->rm_depth) : 0, P.stream, PMC.rmap, PMC.lookup_rad,
-                               d->rm_depth, P.lkq.p, lk_w, P.fgl.p, work);
-            HIPCHK(hipGetLastError());
-          }
-          hipLaunchKernelGGL(k_fg_resolve, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, in_w, qin, P.fgl.p);
-          HIPCHK(hipGetLastError());
-          qin ^= 1;
-        }
-      }
-      hipLaunchKernelGGL(k_pm_finish, dim3(grid_for(n, 64)), dim3(64), 0, P.stream, d->S, Bc, Rc, PMC, n);
-      HIPCHK(hipGetLastError());
-    };
-    auto pt_caustic = [&](const Batch& Bc, long long n) {
-      if (PMC.cmap.n == 0) return;  // !causticMap.ready()
-      hipLaunchKernelGGL(k_pt_caustic, dim3(grid_for(n, 64)), dim3(64), 0, P.stream, d->S, Bc, PMC, n);
-      HIPCHK(hipGetLastError());
-    };
-    auto resolve_ao = [&](const Batch& Bc, const RenderConst& Rc, long long n) {
-      hipLaunchKernelGGL(k_resolve_ao, dim3(grid_for(n)), dim3(256), 0, P.stream, d->S, Bc, Rc, AOC, n);
-      HIPCHK(hipGetLastError());
-    };
-    TileList TL{tiles_dev.p + (size_t)bi * tiles_per_batch, base_dev.p + (size_t)bi * (tiles_per_batch + 1),
-                (int)std::min<size_t>(tiles_per_batch, owned.size() - (size_t)bi * tiles_per_batch),
-                ps.flags ? pix_dev.p + pix_off[bi] : nullptr};
-    if (nc == 0) {  // adaptive pass with nothing to resample in this batch: keep the gather order chain
-      if (bi > 0) HIPCHK(hipStreamWaitEvent(P.stream, d->gather_ev[(bi - 1) % kPipes], 0));
-      HIPCHK(hipEventRecord(d->gather_ev[bi % kPipes], P.stream));
-      continue;
-    }
-    hipLaunchKernelGGL(k_camera, dim3(grid_for(nc)), dim3(256), 0, P.stream, TL, B, R, nc);
-    HIPCHK(hipGetLastError());
-    if (d->spec) {
-      // ---- specular recursion: generations of nodes, host-synchronised
-      auto shade_entries = [&](const Batch& Bc, const RenderConst& Rc, long long n, long long node_base) {
-        HIPCHK(hipMemsetAsync(d->spec_words.p, 0, d->spec_words.n * sizeof(unsigned long long), P.stream));
-        launch = 0;
-        trace(true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
-        hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights, ao), dim3(grid_for(n, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, Bc, Rc, n, qw(0, 0), AOC);
-        HIPCHK(hipGetLastError());
-        trace(false, shadow_src(Bc), Bc.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, Bc.s_occl);
-        hipLaunchKernelGGL(k_resolve_primary, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, n);
-        HIPCHK(hipGetLastError());
-        for (int isub = 0; isub < (path ? nsub : 0); ++isub) {
-          if (isub > 0) {
-            hipLaunchKernelGGL(d->diff_only ? k_path_start<true> : k_path_start<false>, dim3(grid_for(n, YK_BOUNCE_BLOCK)), dim3(YK_BOUNCE_BLOCK), 0, P.stream, d->S, Bc, Rc, n, isub,
-                               qw(isub, 0));
-            HIPCHK(hipGetLastError());
-          }
-          int qin = 1;
-          for (int depth = 1; depth <= bounces; ++depth) {
-            const unsigned long long* in_w = qw(isub, depth - 1);
-            unsigned long long* out_w = qw(isub, depth);
-            trace(true, ray_src(Bc.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, Bc.q_hits[qin], nullptr);
-            hipLaunchKernelGGL(shade_bounce_fn(d->diff_only, d->xl_lights), dim3(grid_for(n, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bc, Rc, in_w, depth,
-                               isub, qin, out_w);
-            HIPCHK(hipGetLastError());
-            trace(false, shadow_src(Bc), Bc.s_idx, RayCount{out_w, 0, 0}, nullptr, Bc.s_occl);
-            hipLaunchKernelGGL(k_resolve_bounce, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, in_w, depth,
-                               qin);
-            HIPCHK(hipGetLastError());
-            qin ^= 1;
-          }
-        }
-        if (pm) pm_entries(Bc, Rc, n);
-        if (cmap) pt_caustic(Bc, n);
-        if (ao) resolve_ao(Bc, Rc, n);
-        hipLaunchKernelGGL(k_finish_spec, dim3(grid_for(n)), dim3(256), 0, P.stream, Bc, Rc, NS, node_base, n);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_spawn, dim3(grid_for(n)), dim3(256), 0, P.stream, d->S, Bc, Rc, NS, node_base, n);
-        HIPCHK(hipGetLastError());
-      };
-      const unsigned long long start = (unsigned long long)nc;
-      HIPCHK(hipMemcpyAsync(NS.count, &start, sizeof start, hipMemcpyHostToDevice, P.stream));
-      shade_entries(B, R, nc, 0);
-      long long g0 = 0, g1 = nc;
-      for (int level = 1; level <= spec_levels; ++level) {
-        unsigned long long cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, NS.count, sizeof cnt, hipMemcpyDeviceToHost, P.stream));
-        HIPCHK(hipStreamSynchronize(P.stream));
-        if ((long long)cnt > NS.cap) return set_error(YK_ERR_INTERNAL, "specular node store overflow");
-        g0 = g1;
-        g1 = (long long)cnt;
-        if (g1 <= g0) break;
-        RenderConst Rl = R;
-        Rl.level = level;
-        for (long long off = g0; off < g1; off += maxc) {
-          const long long n = std::min<long long>(maxc, g1 - off);
-          Batch Bc = B;
-          Bc.p_rays = NS.ray + off;
-          Bc.soffs = NS.soffs + off;
-          Bc.psample = NS.psample + off;
-          shade_entries(Bc, Rl, n, off);
-        }
-      }
-      hipLaunchKernelGGL(k_fold, dim3(grid_for(nc)), dim3(256), 0, P.stream, B, R, NS, nc);
-      HIPCHK(hipGetLastError());
-    }
-    if (!d->spec) {
-    trace(true, ray_src(B.p_rays), nullptr, RayCount{nullptr, 0, nc}, B.p_hits, nullptr);
-    hipLaunchKernelGGL(shade_primary_fn(d->diff_only, d->xl_lights, ao), dim3(grid_for(nc, YK_PRIMARY_BLOCK)), dim3(YK_PRIMARY_BLOCK), 0, P.stream, d->S, B, R, nc, qw(0, 0), AOC);
-    HIPCHK(hipGetLastError());
-    if (!merged) {
-      trace(false, shadow_src(B), B.s_idx, RayCount{qw(0, 0), 0, 0}, nullptr, B.s_occl);
-      hipLaunchKernelGGL(k_resolve_primary, dim3(grid_for(nc)), dim3(256), 0, P.stream, B, R, nc);
-      HIPCHK(hipGetLastError());
-    }
-    if (pm) pm_entries(B, R, nc);
-    if (cmap) pt_caustic(B, nc);
-    if (ao) resolve_ao(B, R, nc);
-    // sub-path index outermost: pathCol is shared across sub-paths and
-    // accumulated in the reference's order (pathtracer.cc:164-298)
-    for (int isub = 0; isub < (path ? nsub : 0); ++isub) {
-      if (isub > 0) {  // sub-path 0's first segment came out of k_shade_primary
-        hipLaunchKernelGGL(d->diff_only ? k_path_start<true> : k_path_start<false>, dim3(grid_for(nc, YK_BOUNCE_BLOCK)), dim3(YK_BOUNCE_BLOCK), 0, P.stream, d->S, B, R, nc, isub,
-                           qw(isub, 0));
-        HIPCHK(hipGetLastError());
-      }
-      int qin = 1;
-      for (int depth = 1; depth <= bounces; ++depth) {
-        const unsigned long long* in_w = qw(isub, depth - 1);
-        unsigned long long* out_w = qw(isub, depth);
-        trace(true, ray_src(B.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, B.q_hits[qin], nullptr);
-        Batch Bd = B;
-        if (merged) {
-          Bd = merged_region(B, depth);
-          Bd.mq_words = qw(0, 0);
-        }
-        hipLaunchKernelGGL(shade_bounce_fn(d->diff_only, d->xl_lights), dim3(grid_for(nc, bounce_block(d->diff_only))), dim3(bounce_block(d->diff_only)), 0, P.stream, d->S, Bd, R, in_w, depth, isub,
-                           qin, out_w);
-        HIPCHK(hipGetLastError());
-        if (!merged) {
-          trace(false, shadow_src(B), B.s_idx, RayCount{out_w, 0, 0}, nullptr, B.s_occl);
-          hipLaunchKernelGGL(k_resolve_bounce, dim3(grid_for(nc)), dim3(256), 0, P.stream, B, R, in_w, depth, qin);
-          HIPCHK(hipGetLastError());
-        }
-        qin ^= 1;
-      }
-    }
-    if (merged) {  // one any-hit launch for the camera hits and all bounces, then one resolve
-      trace(false, shadow_src(B), B.s_idx, RayCount{qw(0, 0), 0, 0, regions}, nullptr, B.s_occl);
-      hipLaunchKernelGGL(k_resolve_merged, dim3(grid_for(nc)), dim3(256), 0, P.stream, B, R, nc, bounces);
-      HIPCHK(hipGetLastError());
-    } else {
-      hipLaunchKernelGGL(k_finish, dim3(grid_for(nc)), dim3(256), 0, P.stream, B, R, nc);
-    }
-    HIPCHK(hipGetLastError());
-    }  // !d->spec
-    // film: in batch order (tile order), whichever pipe ran the batch
-    if (bi > 0) HIPCHK(hipStreamWaitEvent(P.stream, d->gather_ev[(bi - 1) % kPipes], 0));
-    FilmConst Fb = F;
-    Fb.pmap = ps.flags ? pmap_dev.p : nullptr;
-    Fb.tb0 = bi * tiles_per_batch;
-    Fb.tb1 = (int)std::min<size_t>(owned.size(), (size_t)(bi + 1) * tiles_per_batch);
-    const int4 rc = rect_of[bi];
-    const int gx0 = std::max(F.cx0, rc.x + F.olo_x), gy0 = std::max(F.cy0, rc.y + F.olo_y);
-    const int gx1 = std::min(F.cx1, rc.z + F.ohi_x), gy1 = std::min(F.cy1, rc.w + F.ohi_y);
-    const int gw = gx1 - gx0, gh = gy1 - gy0;
-    if (gw > 0 && gh > 0) {
-      const long long npix = nc / spp;  // the batch's pixel slots (spp samples each)
-      hipLaunchKernelGGL(k_pixel_extent, dim3(grid_for(npix * 64)), dim3(256), 0, P.stream, Fb, B.sxy, B.pext, npix);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(k_film_gather, dim3(grid_for((long long)gw * gh)), dim3(256), 0, P.stream, Fb, B.samples,
-                         B.sxy, TL.base, B.pext, d_film, gx0, gy0, gw, gh);
-      HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipEventRecord(d->gather_ev[bi % kPipes], P.stream));
-    samples_total += nc;
-  }
-  unsigned long long acc[kPipes][2 * kAccWords] = {};
-  for (int pi = 0; pi < npipes; ++pi) {
-    Pipe& P = d->pipe[pi];
-    HIPCHK(hipMemcpyAsync(acc[pi], P.words.p, sizeof acc[pi], hipMemcpyDeviceToHost, P.stream));
-    HIPCHK(hipStreamSynchronize(P.stream));
-  }
-  if (std::getenv("YK_LAUNCH_LOG") && !d->spec) {
-    // diagnostic: rays of every traversal launch (queue-count words), per batch
-    for (int bi = 0; bi < nbatch; ++bi) {
-      const int pi = bi % npipes;
-      std::vector<unsigned long long> q((size_t)qwords_per_batch);
-      HIPCHK(hipMemcpy(q.data(), d->pipe[pi].words.p + 2 * kAccWords + words_per_batch * (bi / npipes),
-                       q.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-      std::fprintf(stderr, "[launch-log] batch %d samples %lld:", bi, nc_of[bi]);
-      for (int w = 0; w < qwords_per_batch; ++w)
-        std::fprintf(stderr, " d%d shadow %llu next %llu;", w, q[w] & 0xFFFFFFFFull, q[w] >> 32);
-      std::fprintf(stderr, "\n");
-    }
-  }
-  yk_stats local{};
-  yk_stats* S = st ? st : &local;
-  for (int pi = 0; pi < npipes; ++pi) {
-    if (acc[pi][2] || acc[pi][kAccWords + 2])
-      return set_error(YK_ERR_INTERNAL, "kd-tree traversal watchdog fired (corrupt tree or stack)");
-    S->closest_nodes += acc[pi][0];
-    S->closest_tris += acc[pi][1];
-    S->closest_rays += acc[pi][3];
-    S->shadow_nodes += acc[pi][kAccWords];
-    S->shadow_tris += acc[pi][kAccWords + 1];
-    S->shadow_rays += acc[pi][kAccWords + 3];
-  }
-  for (const Timed& t : timed) {
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, d->pipe[t.pipe].evpool[t.ev], d->pipe[t.pipe].evpool[t.ev + 1]));
-    if (t.closest) {
-      S->ms_closest += ms;
-      S->closest_launches++;
-    } else {
-      S->ms_shadow += ms;
-      S->shadow_launches++;
-    }
-  }
-  S->camera_samples += (uint64_t)samples_total;
-  S->ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (aborted) return set_error(YK_ERR_ABORTED, "render aborted by the abort callback");
-  return YK_OK;
-  YK_GUARD_END
-}
-
-extern "C" {
-
-int yk_render_shard(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, float* d_film,
-                    yk_stats* st) {
-  if (!d || !p || !d_film || nshards < 1 || shard < 0 || shard >= nshards)
-    return set_error(YK_ERR_ARG, "yk_render_shard: bad arguments");
-  if (p->aa_passes < 1) return set_error(YK_ERR_ARG, "AA_passes must be >= 1");
-  const int n0 = std::max(1, p->aa_samples);  // scene_t::setAntialiasing, scene.cc:736-742
-  if (p->aa_passes == 1) return render_pass(d, p, shard, nshards, d_film, st, PassSpec{n0, 0, false, nullptr});
-  // tiledIntegrator_t::render, integrator.cc:132-170: pass 0 everywhere, then
-  // AA_inc_samples more in the pixels imageFilm_t::nextPass flags
-  if (nshards != 1)
-    return set_error(YK_ERR_UNSUPPORTED, "AA_passes > 1 needs the whole film (nshards = 1): nextPass reads it");
-  const int inc = p->aa_inc_samples > 0 ? p->aa_inc_samples : n0;
-  int rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{n0, 0, true, nullptr});
-  if (rc != YK_OK) return rc;  // YK_ERR_ABORTED included: no further passes
-  YK_GUARD_BEGIN
-  const int w = p->width, h = p->height;
-  std::vector<uint8_t> flags((size_t)w * h);
-  DBuf<uint8_t>& flags_dev = d->flags_dev;
-  flags_dev.ensure(flags.size());
-  for (int pass = 1; pass < p->aa_passes; ++pass) {
-    const uint8_t* fl = nullptr;  // AA_threshold <= 0: doMoreSamples is always true
-    if (p->aa_threshold > 0.f) {
-      HIPCHK(hipMemsetAsync(flags_dev.p, 0, flags.size(), d->stream));
-      if (w > 1 && h > 1) {
-        hipLaunchKernelGGL(k_aa_flags, dim3(grid_for((long long)(w - 1) * (h - 1))), dim3(256), 0, d->stream, d_film,
-                           w, h, p->aa_threshold, flags_dev.p);
-        HIPCHK(hipGetLastError());
-      }
-      HIPCHK(hipMemcpyAsync(flags.data(), flags_dev.p, flags.size(), hipMemcpyDeviceToHost, d->stream));
-      HIPCHK(hipStreamSynchronize(d->stream));
-      fl = flags.data();
-    }
-    rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{inc, n0 + (pass - 1) * inc, true, fl});
-    if (rc != YK_OK) return rc;
-  }
-  return YK_OK;
-  YK_GUARD_END
-}
-
-int yk_film_resolve(yk_device* d, const yk_render_params* p, const float* d_film, float* d_rgba) {
-  if (!d || !p || !d_film || !d_rgba) return set_error(YK_ERR_ARG, "yk_film_resolve: NULL argument");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  const long long npx = (long long)p->width * p->height;
-  hipLaunchKernelGGL(k_film_resolve, dim3(grid_for(npx)), dim3(256), 0, d->stream, d_film, d_rgba, npx);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(d->stream));
-  return YK_OK;
-  YK_GUARD_END
-}
-
-int yk_render_film(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, float* film_host,
-                   yk_stats* st) {
-  if (!d || !p || !film_host) return set_error(YK_ERR_ARG, "yk_render_film: NULL argument");
-  if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  const size_t npx = (size_t)p->width * p->height;
-  DBuf<float> film;
-  film.ensure(npx * 5);
-  HIPCHK(hipMemsetAsync(film.p, 0, npx * 5 * sizeof(float), d->stream));
-  const int rc = yk_render_shard(d, p, shard, nshards, film.p, st);
-  if (rc != YK_OK) return rc;
-  HIPCHK(hipMemcpy(film_host, film.p, npx * 5 * sizeof(float), hipMemcpyDeviceToHost));
-  return YK_OK;
-  YK_GUARD_END
-}
-
-// Whole frame on ndev devices (tiledIntegrator_t::render's threads,
-// integrator.cc:177-211, one host thread per device): device i renders the
-// tiles t % ndev == i into its own film; the films are reduced into device
-// 0's by peer copies over xGMI (hipMemcpyPeerAsync) and one add per shard,
-// in shard order. Adaptive passes (AA_passes > 1): after every pass the
-// reduced film gives imageFilm_t::nextPass's flags (k_aa_flags, imagefilm.cc:
-// 213-289), which every device then resamples in its own tiles.
-int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params* p, float* film_host,
-                    yk_stats* st) {
-  if (!devs || ndev < 1 || !p || !film_host) return set_error(YK_ERR_ARG, "yk_render_multi: bad arguments");
-  if (ndev > kMaxMultiDev) return set_error(YK_ERR_UNSUPPORTED, "yk_render_multi: at most 16 devices");
-  for (int i = 0; i < ndev; ++i) {
-    if (!devs[i]) return set_error(YK_ERR_ARG, "yk_render_multi: NULL device");
-    if (!devs[i]->uploaded) return set_error(YK_ERR_STATE, "yk_render_multi: a device has no scene uploaded");
-    for (int j = 0; j < i; ++j)
-      if (devs[j] == devs[i]) return set_error(YK_ERR_ARG, "yk_render_multi: a device handle is listed twice");
-    // one frame = one scene: the same uploaded scene generation everywhere
-    // (handles on one GPU share its constant memory, and shards of different
-    // scenes would be summed into one film)
-    if (devs[i]->uploaded_gen != devs[0]->uploaded_gen || !same_constants(devs[i], devs[0]))
-      return set_error(YK_ERR_STATE, "yk_render_multi: the devices hold different scenes (upload the same scene to all)");
-    const bool maps = p->integrator == YK_INTEGRATOR_PHOTON ||
-                      (p->integrator == YK_INTEGRATOR_PATH &&
-                       (p->caustic_type == YK_CAUSTIC_PHOTON || p->caustic_type == YK_CAUSTIC_BOTH)) ||
-                      (p->integrator == YK_INTEGRATOR_DIRECT && p->dl_caustics != 0);
-    if (maps && (!devs[i]->pm_ready || devs[i]->pm_integrator != p->integrator ||
-                 std::memcmp(&devs[i]->pm_params, &p->photon, sizeof(yk_photon_params)) != 0))
-      return set_error(YK_ERR_STATE, "yk_render_multi: device " + std::to_string(i) +
-                                         " has no photon maps built with these parameters (yk_photon_build)");
-  }
-  if (p->aa_passes < 1) return set_error(YK_ERR_ARG, "AA_passes must be >= 1");
-  if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
-  YK_GUARD_BEGIN
-  const size_t npx = (size_t)p->width * p->height, nfl = npx * 5;
-  yk_device* d0 = devs[0];
-  // shard films and reduce buffers live on the handles: sized once, reused
-  for (int i = 0; i < ndev; ++i) {
-    HIPCHK(hipSetDevice(devs[i]->ordinal));
-    devs[i]->mfilm.ensure(nfl);
-    HIPCHK(hipMemsetAsync(devs[i]->mfilm.p, 0, nfl * sizeof(float), devs[i]->stream));
-    HIPCHK(hipStreamSynchronize(devs[i]->stream));
-    if (devs[i]->ordinal != d0->ordinal) {  // direct xGMI access where the pair allows it
-      int can = 0;
-      HIPCHK(hipDeviceCanAccessPeer(&can, d0->ordinal, devs[i]->ordinal));
-      if (can) {
-        HIPCHK(hipSetDevice(d0->ordinal));
-        const hipError_t e = hipDeviceEnablePeerAccess(devs[i]->ordinal, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) HIPCHK(e);
-        (void)hipGetLastError();
-      }
-    }
-  }
-  HIPCHK(hipSetDevice(d0->ordinal));
-  d0->macc.ensure(nfl);
-  FilmShards FS{};
-  FS.n = ndev;
-  // YK_MULTI_STAGE_ALL=1 (test only): shards on d0's own GPU also take the
-  // peer path (staging film, copy stream, event), so one-GPU boxes run it
-  const bool stage_all = [] {
-    const char* e = std::getenv("YK_MULTI_STAGE_ALL");
-    return e && e[0] == '1';
-  }();
-  auto staged = [&](int i) { return i > 0 && (devs[i]->ordinal != d0->ordinal || stage_all); };
-  for (int i = 0; i < ndev; ++i) {
-    // a shard on d0's own GPU is read in place; a peer GPU's film is copied
-    // into a staging film first, on a copy stream of its own
-    if (!staged(i)) {
-      FS.f[i] = devs[i]->mfilm.p;
-      continue;
-    }
-    d0->mstage[i].ensure(nfl);
-    if (!d0->mstream[i]) HIPCHK(hipStreamCreateWithFlags(&d0->mstream[i], hipStreamNonBlocking));
-    if (!d0->mevent[i]) HIPCHK(hipEventCreateWithFlags(&d0->mevent[i], hipEventDisableTiming));
-    FS.f[i] = d0->mstage[i].p;
-  }
-  std::vector<yk_stats> sts(ndev);
-  double ms_reduce = 0.0;
-  // one pass on every device, each in its own host thread
-  auto run = [&](const PassSpec& ps) -> int {
-    std::vector<int> rc(ndev, YK_OK);
-    std::vector<std::string> msg(ndev);
-    std::vector<std::thread> th;
-    for (int i = 0; i < ndev; ++i)
-      th.emplace_back([&, i] {
-        rc[i] = render_pass(devs[i], p, i, ndev, devs[i]->mfilm.p, &sts[i], ps);
-        if (rc[i] != YK_OK) msg[i] = yk_last_error();
-      });
-    for (auto& t : th) t.join();
-    int out = YK_OK;
-    for (int i = 0; i < ndev; ++i) {
-      if (rc[i] == YK_OK) continue;
-      if (rc[i] != YK_ERR_ABORTED) return set_error(rc[i], "device " + std::to_string(i) + ": " + msg[i]);
-      out = YK_ERR_ABORTED;
-    }
-    return out;
-  };
-  // acc = film[0] + film[1] + ... (shard order) on device 0: every peer copy
-  // is in flight at once (one stream each), then one summing pass
-  auto reduce = [&]() {
-    const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(d0->ordinal));
-    hipStream_t s0 = d0->stream;
-    for (int i = 1; i < ndev; ++i) {
-      if (!staged(i)) continue;
-      HIPCHK(hipMemcpyPeerAsync(d0->mstage[i].p, d0->ordinal, devs[i]->mfilm.p, devs[i]->ordinal, nfl * sizeof(float),
-                                d0->mstream[i]));
-      HIPCHK(hipEventRecord(d0->mevent[i], d0->mstream[i]));
-      HIPCHK(hipStreamWaitEvent(s0, d0->mevent[i], 0));
-    }
-    hipLaunchKernelGGL(k_film_sum, dim3(grid_for(((long long)nfl + 3) / 4)), dim3(256), 0, s0, d0->macc.p, FS,
-                       (long long)nfl);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s0));
-    ms_reduce += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  };
-  const int n0 = std::max(1, p->aa_samples);  // scene_t::setAntialiasing, scene.cc:736-742
-  const bool multipass = p->aa_passes > 1;
-  int rc = run(PassSpec{n0, 0, multipass, nullptr});
-  if (rc != YK_OK && rc != YK_ERR_ABORTED) return rc;
-  reduce();
-  if (multipass && rc == YK_OK) {
-    const int inc = p->aa_inc_samples > 0 ? p->aa_inc_samples : n0;
-    const int w = p->width, h = p->height;
-    std::vector<uint8_t> flags(npx);
-    DBuf<uint8_t>& flags_dev = d0->flags_dev;
-    flags_dev.ensure(npx);
-    for (int pass = 1; pass < p->aa_passes; ++pass) {
-      const uint8_t* fl = nullptr;  // AA_threshold <= 0: doMoreSamples is always true
-      if (p->aa_threshold > 0.f) {
-        HIPCHK(hipSetDevice(d0->ordinal));
-        HIPCHK(hipMemsetAsync(flags_dev.p, 0, npx, d0->stream));
-        if (w > 1 && h > 1) {
-          hipLaunchKernelGGL(k_aa_flags, dim3(grid_for((long long)(w - 1) * (h - 1))), dim3(256), 0, d0->stream,
-                             d0->macc.p, w, h, p->aa_threshold, flags_dev.p);
-          HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(flags.data(), flags_dev.p, npx, hipMemcpyDeviceToHost, d0->stream));
-        HIPCHK(hipStreamSynchronize(d0->stream));
-        fl = flags.data();
-      }
-      rc = run(PassSpec{inc, n0 + (pass - 1) * inc, true, fl});
-      if (rc != YK_OK && rc != YK_ERR_ABORTED) return rc;
-      reduce();
-      if (rc == YK_ERR_ABORTED) break;
-    }
-  }
-  HIPCHK(hipSetDevice(d0->ordinal));
-  HIPCHK(hipMemcpy(film_host, d0->macc.p, nfl * sizeof(float), hipMemcpyDeviceToHost));
-  if (st) {
-    for (const yk_stats& x : sts) {
-      st->closest_rays += x.closest_rays;
-      st->shadow_rays += x.shadow_rays;
-      st->closest_nodes += x.closest_nodes;
-      st->closest_tris += x.closest_tris;
-      st->shadow_nodes += x.shadow_nodes;
-      st->shadow_tris += x.shadow_tris;
-      st->camera_samples += x.camera_samples;
-      st->ms_total = std::max(st->ms_total, x.ms_total);
-      st->ms_closest += x.ms_closest;
-      st->ms_shadow += x.ms_shadow;
-      st->closest_launches += x.closest_launches;
-      st->shadow_launches += x.shadow_launches;
-    }
-    st->ms_reduce += ms_reduce;
-  }
-  if (rc == YK_ERR_ABORTED) return set_error(rc, "render aborted by the abort callback (film holds the finished batches)");
-  return YK_OK;
-  YK_GUARD_END
-}
-
-int yk_render(yk_device* d, const yk_render_params* p, float* rgba_host, yk_stats* st) {
-  if (!d || !p || !rgba_host) return set_error(YK_ERR_ARG, "yk_render: NULL argument");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  const size_t npx = (size_t)p->width * p->height;
-  float *film = nullptr, *rgba = nullptr;
-  HIPCHK(hipMalloc(&film, npx * 5 * sizeof(float)));
-  HIPCHK(hipMalloc(&rgba, npx * 4 * sizeof(float)));
-  HIPCHK(hipMemsetAsync(film, 0, npx * 5 * sizeof(float), d->stream));
-  int rc = yk_render_shard(d, p, 0, 1, film, st);
-  if (rc == YK_OK) rc = yk_film_resolve(d, p, film, rgba);
-  if (rc == YK_OK) HIPCHK(hipMemcpy(rgba_host, rgba, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
-  (void)hipFree(film);
-  (void)hipFree(rgba);
-  return rc;
-  YK_GUARD_END
-}
-
-}  // extern "C"
+#include "yk_render_host.inc"

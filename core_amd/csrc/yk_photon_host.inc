@@ -186,16 +186,14 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
     HIPCHK(hipMemsetAsync(words.p, 0, nw * sizeof(unsigned long long), P.stream));
     HIPCHK(hipMemsetAsync(s_flag.p, 0, nslots, P.stream));
     unsigned long long* qwd = words.p + kAccWords;
-    hipLaunchKernelGGL(k_photon_emit, dim3(grid_for(N, YK_APPEND_BLOCK)), dim3(YK_APPEND_BLOCK), 0, P.stream, C, PB, qwd);
-    HIPCHK(hipGetLastError());
+    launch(k_photon_emit, grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, C, PB, qwd);
     int qin = 1;
     for (int b = 0; b <= MB; ++b) {
       unsigned long long* work = words.p + kAccWords + (MB + 2) + 128ll * b;
       enqueue_trace<true>(d, P, ray_src(PB.q_rays[qin]), nullptr, RayCount{qwd + b, 32, 0}, PB.q_hits[qin], nullptr, work,
                           words.p, nullptr, nullptr);
-      hipLaunchKernelGGL(k_photon_hit, dim3(grid_for(N, YK_APPEND_BLOCK)), dim3(YK_APPEND_BLOCK), 0, P.stream, d->S, C, PB, b, qwd + b, qin,
-                         qwd + b + 1);
-      HIPCHK(hipGetLastError());
+      launch(k_photon_hit, grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, d->S, C, PB, b, qwd + b, qin,
+             qwd + b + 1);
       qin ^= 1;
     }
     unsigned long long acc[kAccWords];
@@ -334,9 +332,8 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
     const PMapDev dmap{d->dm_nodes.p, d->dm_pos.p, d->dm_dir.p, d->dm_col.p, ndm};
     const float iscale = (float)(1.0 / ((double)(float)dpaths * YK_PI_D));
     auto tp = std::chrono::steady_clock::now();
-    hipLaunchKernelGGL(k_pregather, dim3(grid_for(nr, 64)), dim3(64), 0, P.stream, dmap, dp.p, dn.p, dr.p, dt.p, nr,
-                       q.diffuse_radius * q.diffuse_radius, iscale, q.search, dc.p);
-    HIPCHK(hipGetLastError());
+    launch(k_pregather, grid_for(nr, 64), 64, 0, P.stream, dmap, dp.p, dn.p, dr.p, dt.p, nr,
+           q.diffuse_radius * q.diffuse_radius, iscale, q.search, dc.p);
     std::vector<float4> col(nr);
     HIPCHK(hipMemcpyAsync(col.data(), dc.p, nr * sizeof(float4), hipMemcpyDeviceToHost, P.stream));
     HIPCHK(hipStreamSynchronize(P.stream));
