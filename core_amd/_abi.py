@@ -24,6 +24,7 @@ YK_CAUSTIC_NONE, YK_CAUSTIC_PATH, YK_CAUSTIC_PHOTON, YK_CAUSTIC_BOTH = 0, 1, 2, 
 YK_BOKEH_DISK1, YK_BOKEH_DISK2, YK_BOKEH_TRI, YK_BOKEH_SQR, YK_BOKEH_PENTA, YK_BOKEH_HEXA, YK_BOKEH_RING = \
     0, 1, 3, 4, 5, 6, 7
 YK_BOKEH_BIAS_NONE, YK_BOKEH_BIAS_CENTER, YK_BOKEH_BIAS_EDGE = 0, 1, 2
+YK_CAMERA_PERSPECTIVE, YK_CAMERA_ARCHITECT, YK_CAMERA_ORTHOGRAPHIC, YK_CAMERA_ANGULAR = 0, 1, 2, 3
 YK_MODE_TRIANGLE, YK_MODE_UNIVERSAL = 0, 1
 YK_MESH_TRIM, YK_MESH_VTRIM = 0, 1
 
@@ -53,7 +54,10 @@ class yk_camera(C.Structure):
     _fields_ = [("from_", f3), ("to", f3), ("up", f3), ("resx", C.c_int32), ("resy", C.c_int32),
                 ("focal", C.c_float), ("aspect_ratio", C.c_float), ("near_clip", C.c_float),
                 ("far_clip", C.c_float), ("aperture", C.c_float), ("dof_distance", C.c_float),
-                ("bokeh_type", C.c_int32), ("bokeh_bias", C.c_int32), ("bokeh_rotation", C.c_float)]
+                ("bokeh_type", C.c_int32), ("bokeh_bias", C.c_int32), ("bokeh_rotation", C.c_float),
+                # appended: the camera kind and the orthographic / angular parameters
+                ("type", C.c_int32), ("circular", C.c_int32), ("mirrored", C.c_int32), ("reserved0", C.c_int32),
+                ("scale", C.c_double), ("angle", C.c_double), ("max_angle", C.c_double)]
 
 
 class yk_material_state(C.Structure):
@@ -90,7 +94,10 @@ class yk_camera_state(C.Structure):
     _fields_ = [("position", f3), ("vright", f3), ("vup", f3), ("vto", f3), ("cam_z", f3),
                 ("near_p", f3), ("far_p", f3), ("resx", C.c_int32), ("resy", C.c_int32),
                 ("aperture", C.c_float), ("dof_distance", C.c_float), ("dof_rt", f3), ("dof_up", f3),
-                ("bokeh_type", C.c_int32), ("bokeh_bias", C.c_int32), ("lens_ls", C.c_float * 16)]
+                ("bokeh_type", C.c_int32), ("bokeh_bias", C.c_int32), ("lens_ls", C.c_float * 16),
+                # appended: which shootRay runs and the angular camera's constants
+                ("kind", C.c_int32), ("hor_phi", C.c_float), ("max_r", C.c_float), ("circular", C.c_int32),
+                ("aspect_ratio", C.c_float)]
 
 
 class yk_photon_params(C.Structure):

@@ -216,6 +216,40 @@ yk_camera_state camera_state(const yk_camera& c) {  // camera_t ctor + setAxis
   put(o.cam_z, camZ);
   put(o.near_p, hadd(pos, hmul(c.near_clip, camZ)));
   put(o.far_p, hadd(pos, hmul(c.far_clip, camZ)));
+  o.resx = c.resx;
+  o.resy = c.resy;
+  // The cameras below are restated in source order with the types the
+  // reference's operators give each expression; how its -ffast-math build
+  // orders them is not known (unpinned).
+  if (c.type == YK_CAMERA_ORTHOGRAPHIC) {
+    // orthoCam_t::setAxis (orthographicCamera.cc:37-49); the factory's double
+    // scale reaches the ctor as PFLOAT. 0.5 * scale is a double product handed
+    // to operator*(PFLOAT, vector3d_t); scale / (PFLOAT)res a float division.
+    const float scale = (float)c.scale;
+    hv3 vright = camX, vup = hmul(aspect, camY);
+    put(o.vto, camZ);
+    put(o.position, hsub(pos, hmul((float)(0.5 * (double)scale), hadd(vup, vright))));
+    const float sy = scale / (float)c.resy, sx = scale / (float)c.resx;
+    put(o.vup, {vup.x * sy, vup.y * sy, vup.z * sy});
+    put(o.vright, {vright.x * sx, vright.y * sx, vright.z * sx});
+    o.kind = YK_CAMERA_ORTHOGRAPHIC;
+    return o;
+  }
+  if (c.type == YK_CAMERA_ANGULAR) {
+    // angularCam_t ctor + setAxis + the factory's tail (angularCamera.cc:27-47,
+    // 96-98): hor_phi(angle * M_PI / 180.f) with the PFLOAT ctor argument,
+    // vright *= -1.0 when mirrored, max_r = max_angle / angle in double
+    const float angle = (float)c.angle;
+    o.hor_phi = (float)((double)angle * 3.14159265358979323846 / (double)180.f);
+    put(o.vright, c.mirrored ? hmul(-1.0f, camX) : camX);
+    put(o.vup, camY);
+    put(o.vto, camZ);
+    o.max_r = (float)(c.max_angle / c.angle);
+    o.circular = c.circular ? 1 : 0;
+    o.aspect_ratio = aspect;
+    o.kind = YK_CAMERA_ANGULAR;
+    return o;
+  }
   // depth of field: setAxis's dof_rt / dof_up, the ctor's polygon table
   // (perspectiveCamera.cc:29-50, 57-62)
   o.aperture = c.aperture;
@@ -234,13 +268,13 @@ yk_camera_state camera_state(const yk_camera& c) {  // camera_t ctor + setAxis
       w += wi;
     }
   }
-  const hv3 vright = camX, vup = hmul(aspect, camY);
+  // architectCam_t::setAxis (architectCamera.cc:54-68) differs in vup alone:
+  // aspect_ratio * vector3d_t(0, 0, -1); its ctor repeats the lens table above
+  const hv3 vright = camX, vup = hmul(aspect, c.type == YK_CAMERA_ARCHITECT ? hv3{0.f, 0.f, -1.f} : camY);
   put(o.vto, hsub(hmul(c.focal, camZ), hmul(0.5f, hadd(vup, vright))));
   const float ry = 1.0f / (float)c.resy, rx = 1.0f / (float)c.resx;  // compiled form of "/= res"
   put(o.vup, {vup.x * ry, vup.y * ry, vup.z * ry});
   put(o.vright, {vright.x * rx, vright.y * rx, vright.z * rx});
-  o.resx = c.resx;
-  o.resy = c.resy;
   return o;
 }
 

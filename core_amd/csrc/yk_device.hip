@@ -32,6 +32,7 @@
 #include "../../include/yk_api.h"
 #include "../../include/yk_test_hooks.h"
 #include "../../include/yk_test_hooks_light.h"
+#include "../../include/yk_test_hooks_camera.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"
@@ -90,12 +91,18 @@ struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-4
   float sq_radius, sq_radius_eps;
 };
 
-struct DCam {  // perspectiveCam_t after camera_t ctor + setAxis
+struct DCam {  // the camera after camera_t ctor + setAxis (yk_camera_state)
   float pos[3], vright[3], vup[3], vto[3], camZ[3], near_p[3], far_p[3];
   // depth of field (aperture != 0): dof_rt, dof_up, dof_distance, bokeh, LS
   float aperture, dof_distance, dof_rt[3], dof_up[3];
   int bokeh_type, bokeh_bias;
   float ls[16];
+  // which shootRay runs (YK_CAMERA_PERSPECTIVE, _ORTHOGRAPHIC, _ANGULAR), and
+  // angularCam_t's constants: (PFLOAT)resx / resy, camera_t::aspect_ratio,
+  // hor_phi, max_r, circular. All zero for the perspective kind.
+  int kind;
+  float resx, resy, aspect, hor_phi, max_r;
+  int circular;
 };
 
 constexpr int kMaxMats = 64;
@@ -2409,10 +2416,108 @@ __device__ __forceinline__ void lens_uv(float r1, float r2, float& u, float& v) 
   }
 }
 
-__global__ void __launch_bounds__(256) k_camera(TileList TL, Batch B, RenderConst R, long long nc) {
-  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  int s, j, i;
+// camera_t::shootRay of the scene's camera kind -> wt. Shared by k_camera and
+// the test hook (yk_debug_camera_rays).
+// ray_plane_intersection (geometry.h:33-36) for the near / far planes
+__device__ __forceinline__ void cam_clip(yk_ray& r, v3 from, v3 d) {
+  const v3 cz = ld3(c_cam.camZ);
+  const float den = vdot(d, cz);
+  r.tmin = vdot(cz, vsub(ld3(c_cam.near_p), from)) / den;
+  r.tmax = vdot(cz, vsub(ld3(c_cam.far_p), from)) / den;
+}
+template <int KIND>
+__device__ __forceinline__ float cam_shoot(float px, float py, float lu, float lv, yk_ray& r);
+
+// perspectiveCam_t::shootRay (perspectiveCamera.cc:127-149), an architect
+// camera's too; lu, lv are read with an aperture only
+template <>
+__device__ __forceinline__ float cam_shoot<YK_CAMERA_PERSPECTIVE>(float px, float py, float lu, float lv, yk_ray& r) {
+  const v3 vr = ld3(c_cam.vright), vu = ld3(c_cam.vup), vt = ld3(c_cam.vto);
+  v3 d = vadd(vadd(vmul(px, vr), vmul(py, vu)), vt);
+  d = vnormalize_cam(d);
+  const v3 from = ld3(c_cam.pos);
+  r.from[0] = from.x;
+  r.from[1] = from.y;
+  r.from[2] = from.z;
+  r.dir[0] = d.x;
+  r.dir[1] = d.y;
+  r.dir[2] = d.z;
+  cam_clip(r, from, d);
+  if (c_cam.aperture != 0.f) {
+    // shootRay's aperture branch (perspectiveCamera.cc:139-147): tmin / tmax
+    // stay those of the pinhole ray
+    float u, v;
+    lens_uv(lu, lv, u, v);
+    const v3 LI = vadd(vmul(u, ld3(c_cam.dof_rt)), vmul(v, ld3(c_cam.dof_up)));
+    const v3 f2 = vadd(from, LI);
+    const v3 d2 = vnormalize_cam(vsub(vmul(c_cam.dof_distance, d), LI));
+    r.from[0] = f2.x;
+    r.from[1] = f2.y;
+    r.from[2] = f2.z;
+    r.dir[0] = d2.x;
+    r.dir[1] = d2.y;
+    r.dir[2] = d2.z;
+  }
+  return 1.f;
+}
+
+// orthoCam_t::shootRay (orthographicCamera.cc:52-64): c_cam.pos is its `pos`,
+// the direction vto = camZ is not normalised again; no lens. Source order;
+// not pinned against the compiled reference.
+template <>
+__device__ __forceinline__ float cam_shoot<YK_CAMERA_ORTHOGRAPHIC>(float px, float py, float, float, yk_ray& r) {
+  const v3 from = vadd(vadd(ld3(c_cam.pos), vmul(px, ld3(c_cam.vright))), vmul(py, ld3(c_cam.vup)));
+  const v3 d = ld3(c_cam.vto);
+  r.from[0] = from.x;
+  r.from[1] = from.y;
+  r.from[2] = from.z;
+  r.dir[0] = d.x;
+  r.dir[1] = d.y;
+  r.dir[2] = d.z;
+  cam_clip(r, from, d);
+  return 1.f;
+}
+
+// angularCam_t::shootRay (angularCamera.cc:49-71), source order in float;
+// fSqrt is sqrtf, fSin / fCos the FAST_TRIG forms. atan2 is the one libm call:
+// the device's atan2f is not bit-pinned to glibc's. Outside
+// the circle (circular, radius > max_r) wt = 0 and the reference returns its
+// default ray_t (tmin 0, tmax -1) from the camera's position, direction unset:
+// here direction 0, which is how k_dead_samples knows the sample.
+template <>
+__device__ __forceinline__ float cam_shoot<YK_CAMERA_ANGULAR>(float px, float py, float, float, yk_ray& r) {
+  const v3 from = ld3(c_cam.pos);
+  r.from[0] = from.x;
+  r.from[1] = from.y;
+  r.from[2] = from.z;
+  const float u = 1.f - 2.f * (px / c_cam.resx);
+  float v = 2.f * (py / c_cam.resy) - 1.f;
+  v *= c_cam.aspect;
+  const float radius = sqrtf(u * u + v * v);
+  if (c_cam.circular && radius > c_cam.max_r) {
+    r.dir[0] = 0.f;
+    r.dir[1] = 0.f;
+    r.dir[2] = 0.f;
+    r.tmin = 0.f;
+    r.tmax = -1.0f;
+    return 0.f;
+  }
+  float theta = 0.f;
+  if (!((u == 0.f) && (v == 0.f))) theta = atan2f(v, u);
+  const float phi = radius * c_cam.hor_phi;
+  const v3 d = vadd(vmul(fsin_ref(phi), vadd(vmul(fcos_ref(theta), ld3(c_cam.vright)),
+                                             vmul(fsin_ref(theta), ld3(c_cam.vup)))),
+                    vmul(fcos_ref(phi), ld3(c_cam.vto)));
+  r.dir[0] = d.x;
+  r.dir[1] = d.y;
+  r.dir[2] = d.z;
+  cam_clip(r, from, d);
+  return 1.f;
+}
+
+// Sample s of pixel (j, i) that camera-sample index c of the batch stands for
+__device__ __forceinline__ void cam_sample_of(const TileList& TL, const RenderConst& R, long long c, int& s, int& j,
+                                              int& i) {
   if (TL.pix) {  // adaptive pass: only the flagged pixels, in tile / row order
     // 32-bit index arithmetic: a batch holds far fewer than 2^31 samples
     const int packed = TL.pix[(unsigned)c / (unsigned)R.spp];
@@ -2433,61 +2538,91 @@ __global__ void __launch_bounds__(256) k_camera(TileList TL, Batch B, RenderCons
     j = T.x + pl % T.z;
     i = T.y + pl / T.z;
   }
-  const unsigned so = fnv32a((unsigned)i * fnv32a((unsigned)j));
-  const unsigned psample = (unsigned)(R.pass_off + s);  // rstate.pixelSample = pass_offs + sample
-  B.soffs[c] = so;
-  if (R.ps) B.psample[c] = psample;
-  float dx = 0.5f, dy = 0.5f;
-  if (R.multipass) {
-    dx = ri_vdc(psample, so);
-    dy = ri_s(psample, so);
-  } else if (R.spp > 1) {
-    dx = (0.5f + (float)s) * R.d1;
-    dy = ri_lp((unsigned)s + so, 0u);
+}
+
+// One instantiation per shootRay. live (an angular camera with `circular`
+// only, else nullptr): the samples that carry a ray are appended to a queue --
+// their indices to live_idx, the count to *live -- and the primary trace runs
+// over that queue alone, so a sample outside the circle (wt = 0,
+// integrator.cc:293-297) is never traced or counted. Its hit record is a miss:
+// the shading kernels start nothing for it, and k_dead_samples zeroes the
+// sample they give a miss before the film gathers it.
+template <int KIND>
+__global__ void __launch_bounds__(256) k_camera(TileList TL, Batch B, RenderConst R, long long nc,
+                                                unsigned long long* __restrict__ live,
+                                                unsigned* __restrict__ live_idx) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (KIND != YK_CAMERA_ANGULAR) {
+    if (c >= nc) return;
   }
-  B.sxy[c] = make_float2(dx, dy);
-  const float px = (float)j + dx, py = (float)i + dy;
-  const v3 vr = ld3(c_cam.vright), vu = ld3(c_cam.vup), vt = ld3(c_cam.vto), cz = ld3(c_cam.camZ);
-  v3 d = vadd(vadd(vmul(px, vr), vmul(py, vu)), vt);
-  d = vnormalize_cam(d);
-  const v3 from = ld3(c_cam.pos);
-  yk_ray r;
-  r.from[0] = from.x;
-  r.from[1] = from.y;
-  r.from[2] = from.z;
-  r.dir[0] = d.x;
-  r.dir[1] = d.y;
-  r.dir[2] = d.z;
-  const float den = vdot(d, cz);
-  r.tmin = vdot(cz, vsub(ld3(c_cam.near_p), from)) / den;
-  r.tmax = vdot(cz, vsub(ld3(c_cam.far_p), from)) / den;
-  if (c_cam.aperture != 0.f) {
-    // renderTile's lens samples (integrator.cc:248-291): Halton(3) / Halton(5)
-    // set to pass_offs + samplingOffs per pixel, one getNext per sample in
-    // sample order -- so sample s takes the (s+1)-th value
-    Halton hu, hv;
-    hal_start(hu, 3u, (unsigned)R.pass_off + so);
-    hal_start(hv, 5u, (unsigned)R.pass_off + so);
-    float lu = 0.f, lv = 0.f;
-    for (int k = 0; k <= s; ++k) {
-      lu = hal_next(hu);
-      lv = hal_next(hv);
+  const bool valid = c < nc;
+  int s = 0, j = 0, i = 0;
+  if (valid) cam_sample_of(TL, R, c, s, j, i);
+  float wt = 0.f;
+  if (valid) {
+    const unsigned so = fnv32a((unsigned)i * fnv32a((unsigned)j));
+    const unsigned psample = (unsigned)(R.pass_off + s);  // rstate.pixelSample = pass_offs + sample
+    B.soffs[c] = so;
+    if (R.ps) B.psample[c] = psample;
+    float dx = 0.5f, dy = 0.5f;
+    if (R.multipass) {
+      dx = ri_vdc(psample, so);
+      dy = ri_s(psample, so);
+    } else if (R.spp > 1) {
+      dx = (0.5f + (float)s) * R.d1;
+      dy = ri_lp((unsigned)s + so, 0u);
     }
-    // shootRay's aperture branch (perspectiveCamera.cc:139-147): tmin / tmax
-    // stay those of the pinhole ray
-    float u, v;
-    lens_uv(lu, lv, u, v);
-    const v3 LI = vadd(vmul(u, ld3(c_cam.dof_rt)), vmul(v, ld3(c_cam.dof_up)));
-    const v3 f2 = vadd(from, LI);
-    const v3 d2 = vnormalize_cam(vsub(vmul(c_cam.dof_distance, d), LI));
-    r.from[0] = f2.x;
-    r.from[1] = f2.y;
-    r.from[2] = f2.z;
-    r.dir[0] = d2.x;
-    r.dir[1] = d2.y;
-    r.dir[2] = d2.z;
+    B.sxy[c] = make_float2(dx, dy);
+    const float px = (float)j + dx, py = (float)i + dy;
+    float lu = 0.5f, lv = 0.5f;
+    if constexpr (KIND == YK_CAMERA_PERSPECTIVE) {
+      if (c_cam.aperture != 0.f) {
+        // renderTile's lens samples (integrator.cc:248-291): Halton(3) / Halton(5)
+        // set to pass_offs + samplingOffs per pixel, one getNext per sample in
+        // sample order -- so sample s takes the (s+1)-th value
+        Halton hu, hv;
+        hal_start(hu, 3u, (unsigned)R.pass_off + so);
+        hal_start(hv, 5u, (unsigned)R.pass_off + so);
+        for (int k = 0; k <= s; ++k) {
+          lu = hal_next(hu);
+          lv = hal_next(hv);
+        }
+      }
+    }
+    yk_ray r;
+    wt = cam_shoot<KIND>(px, py, lu, lv, r);
+    B.p_rays[c] = r;
+    if constexpr (KIND == YK_CAMERA_ANGULAR) {
+      if (live && wt == 0.f) B.p_hits[c] = yk_hit{-1, 0.f, 0.f, 0.f};
+    }
   }
-  B.p_rays[c] = r;
+  if constexpr (KIND == YK_CAMERA_ANGULAR) {
+    if (live) {  // kernel argument: uniform
+      // one atomic per wave; the queue's order is free (results go to slot c)
+      const bool alive = valid && wt != 0.f;
+      const unsigned long long m = __ballot(alive);
+      if (m != 0ull) {
+        const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int leader = __ffsll((long long)m) - 1;
+        unsigned long long base = 0;
+        if ((int)(threadIdx.x & 63u) == leader) base = atomicAdd(live, (unsigned long long)__popcll(m));
+        base = shfl_u64(base, leader);
+        if (alive) live_idx[base + rank] = (unsigned)c;
+      }
+    }
+  }
+}
+
+// The samples of an angular camera that carry no ray (wt = 0): renderTile
+// splats colorA_t(0) for them (integrator.cc:293-297), colour and alpha zero,
+// whatever the background is. They are the camera rays with direction 0
+// (cam_shoot). Launched only for a camera that can have them.
+__global__ void __launch_bounds__(256) k_dead_samples(Batch B, long long nc) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const yk_ray& r = B.p_rays[c];
+  if (r.dir[0] == 0.f && r.dir[1] == 0.f && r.dir[2] == 0.f && r.tmin == 0.f && r.tmax == -1.0f)
+    B.samples[c] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 // Ray records streamed to the next kernel (shadow slots, bounce queues) are
@@ -4178,6 +4313,9 @@ struct yk_device {
   DBuf<int4> tiles_dev;
   DBuf<int> base_dev, pix_dev, pmap_dev, rank_dev;
   DBuf<uint8_t> flags_dev;
+  // per batch of a render: the camera samples that carry a ray (an angular
+  // camera with `circular`; unused otherwise)
+  DBuf<unsigned long long> cam_live;
   // the last render's batch plan (yk_debug_last_plan)
   yk_batch_plan last_plan{};
   bool last_plan_valid = false;
@@ -4289,6 +4427,15 @@ DCam make_cam(const yk_camera_state& c) {
   C.bokeh_type = c.bokeh_type;
   C.bokeh_bias = c.bokeh_bias;
   std::memcpy(C.ls, c.lens_ls, sizeof C.ls);
+  C.kind = c.kind == YK_CAMERA_ARCHITECT ? YK_CAMERA_PERSPECTIVE : c.kind;
+  if (C.kind == YK_CAMERA_ANGULAR) {
+    C.resx = (float)c.resx;
+    C.resy = (float)c.resy;
+    C.aspect = c.aspect_ratio;
+    C.hor_phi = c.hor_phi;
+    C.max_r = c.max_r;
+    C.circular = c.circular ? 1 : 0;
+  }
   return C;
 }
 

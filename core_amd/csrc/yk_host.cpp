@@ -2,6 +2,7 @@
 // fixture generation, error reporting. No GPU needed; exercised by the CPU
 // tests and by the oracle harness.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -287,6 +288,18 @@ int yk_scene_get_background(const yk_scene* s, float* rgb_out, int32_t* has_out)
 int yk_scene_set_camera(yk_scene* s, const yk_camera* c) {
   if (!s || !c) return set_error(YK_ERR_ARG, "yk_scene_set_camera: NULL argument");
   if (c->resx <= 0 || c->resy <= 0) return set_error(YK_ERR_ARG, "camera resolution must be > 0");
+  if (c->type < YK_CAMERA_PERSPECTIVE || c->type > YK_CAMERA_ANGULAR)
+    return set_error(YK_ERR_UNSUPPORTED, "unknown camera type");
+  const bool lensless = c->type == YK_CAMERA_ORTHOGRAPHIC || c->type == YK_CAMERA_ANGULAR;
+  if (c->type == YK_CAMERA_ORTHOGRAPHIC && !(std::isfinite(c->scale) && c->scale > 0.0))
+    return set_error(YK_ERR_ARG, "orthographic camera: scale must be finite and > 0");
+  if (c->type == YK_CAMERA_ANGULAR && !(std::isfinite(c->angle) && c->angle > 0.0))
+    return set_error(YK_ERR_ARG, "angular camera: angle must be finite and > 0");
+  if (c->type == YK_CAMERA_ANGULAR && !(std::isfinite(c->max_angle) && c->max_angle >= 0.0))
+    return set_error(YK_ERR_ARG, "angular camera: max_angle must be finite and >= 0");
+  // camera_t::sampleLense() is false for them: an aperture would be dropped
+  if (lensless && c->aperture != 0.f)
+    return set_error(YK_ERR_ARG, "orthographic and angular cameras have no lens: aperture must be 0");
   YK_GUARD_BEGIN
   s->s.set_camera(*c);
   return YK_OK;
@@ -296,7 +309,15 @@ int yk_scene_set_camera(yk_scene* s, const yk_camera* c) {
 int yk_scene_set_camera_state(yk_scene* s, const yk_camera_state* c) {
   if (!s || !c) return set_error(YK_ERR_ARG, "yk_scene_set_camera_state: NULL argument");
   if (c->resx <= 0 || c->resy <= 0) return set_error(YK_ERR_ARG, "camera resolution must be > 0");
-  s->s.set_camera_state(*c);
+  if (c->kind < YK_CAMERA_PERSPECTIVE || c->kind > YK_CAMERA_ANGULAR)
+    return set_error(YK_ERR_UNSUPPORTED, "unknown camera kind");
+  if ((c->kind == YK_CAMERA_ORTHOGRAPHIC || c->kind == YK_CAMERA_ANGULAR) && c->aperture != 0.f)
+    return set_error(YK_ERR_ARG, "orthographic and angular cameras have no lens: aperture must be 0");
+  yk_camera_state k = *c;
+  // an architect camera's shootRay is perspectiveCam_t's: one kind
+  if (k.kind == YK_CAMERA_ARCHITECT) k.kind = YK_CAMERA_PERSPECTIVE;
+  k.circular = k.circular ? 1 : 0;
+  s->s.set_camera_state(k);
   return YK_OK;
 }
 

@@ -316,6 +316,10 @@ struct Timed {
   bool closest;
 };
 
+// An angular camera with `circular` set gives the samples outside its circle
+// no ray (wt = 0): only then do renders keep a live-sample queue.
+bool cam_can_die(const yk_device* d) { return d->cam_host.kind == YK_CAMERA_ANGULAR && d->cam_host.circular != 0; }
+
 // What enqueueing one batch needs: the batch's pipe and buffers, its word
 // block and launch cursor, and the render's list of timed trace launches.
 struct BatchCtx {
@@ -333,6 +337,9 @@ struct BatchCtx {
   Batch B;
   unsigned long long* bw;  // the batch's words (FramePlan)
   int launch;              // hand-out blocks taken
+  // the batch's live camera-sample count (d->cam_live), nullptr unless the
+  // camera can have samples without a ray (cam_can_die)
+  unsigned long long* live = nullptr;
 };
 
 unsigned long long* qw(const BatchCtx& c, int isub, int depth) { return c.bw + isub * (c.fp->bounces + 1) + depth; }
@@ -412,7 +419,10 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
     HIPCHK(hipMemsetAsync(d->spec_words.p, 0, d->spec_words.n * sizeof(unsigned long long), s));
     c.launch = 0;
   }
-  trace(c, true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
+  // camera rays of a camera with dead samples: the live ones' queue (k_camera;
+  // the shadow queue's buffer, which k_shade_primary fills only afterwards)
+  if (c.live && node_base == 0) trace(c, true, ray_src(Bc.p_rays), Bc.s_idx, RayCount{c.live, 0, 0}, Bc.p_hits, nullptr);
+  else trace(c, true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
   launch(shade_primary_fn(d->diff_only, d->xl_lights, fp.ao), grid_for(n, YK_PRIMARY_BLOCK), YK_PRIMARY_BLOCK, 0, s,
          d->S, Bc, Rc, n, qw(c, 0, 0), fp.AOC);
   if (!merged) {
@@ -506,13 +516,26 @@ int enqueue_batch(BatchCtx& c, int bi) {
   const int tb0 = bi * tpb, tb1 = (int)std::min<size_t>(fp.owned.size(), (size_t)(bi + 1) * tpb);
   const TileList TL{d->tiles_dev.p + (size_t)tb0, d->base_dev.p + (size_t)bi * (tpb + 1), tb1 - tb0,
                     c.ps->flags ? d->pix_dev.p + fp.pix_off[bi] : nullptr};
+  c.live = cam_can_die(d) ? d->cam_live.p + bi : nullptr;
   if (nc > 0) {  // else an adaptive pass with nothing to resample in this batch
-    launch(k_camera, grid_for(nc), 256, 0, P.stream, TL, B, fp.R, nc);
+    // one instantiation per shootRay; a perspective or architect camera runs
+    // the first, whose per-sample code is the only one those scenes launch
+    switch (d->cam_host.kind) {
+      case YK_CAMERA_ORTHOGRAPHIC:
+        launch(k_camera<YK_CAMERA_ORTHOGRAPHIC>, grid_for(nc), 256, 0, P.stream, TL, B, fp.R, nc, nullptr, nullptr);
+        break;
+      case YK_CAMERA_ANGULAR:
+        launch(k_camera<YK_CAMERA_ANGULAR>, grid_for(nc), 256, 0, P.stream, TL, B, fp.R, nc, c.live, B.s_idx);
+        break;
+      default:
+        launch(k_camera<YK_CAMERA_PERSPECTIVE>, grid_for(nc), 256, 0, P.stream, TL, B, fp.R, nc, nullptr, nullptr);
+    }
     if (d->spec) {
       if (const int rc = enqueue_spec_generations(c, nc)) return rc;
     } else {
       enqueue_entries(c, B, fp.R, nc, 0);
     }
+    if (c.live) launch(k_dead_samples, grid_for(nc), 256, 0, P.stream, B, nc);
   }
   // film: in batch order (tile order), whichever pipe ran the batch; an
   // empty batch keeps the chain of gather events
@@ -571,6 +594,14 @@ int collect_stats(yk_device* d, const FramePlan& fp, const std::vector<Timed>& t
     HIPCHK(hipEventElapsedTime(&ms, d->pipe[t.pipe].evpool[t.ev], d->pipe[t.pipe].evpool[t.ev + 1]));
     add_trace_stats(S, t.closest, 0, 0, 0, ms);
   }
+  // camera samples that carry a ray: all of them, unless the camera can have
+  // dead ones (the batches' live counts; the pipes are synchronised by now)
+  if (cam_can_die(d)) {
+    std::vector<unsigned long long> live((size_t)fp.plan.nbatch);
+    HIPCHK(hipMemcpy(live.data(), d->cam_live.p, live.size() * sizeof live[0], hipMemcpyDeviceToHost));
+    samples_total = 0;
+    for (const unsigned long long n : live) samples_total += (long long)n;
+  }
   S->camera_samples += (uint64_t)samples_total;
   S->ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return YK_OK;
@@ -590,6 +621,11 @@ int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, int32_t 
   d->last_plan_valid = true;
   d->last_max_batches = (nbatch + npipes - 1) / npipes;
   upload_frame_plan(d, fp);
+  if (cam_can_die(d)) {  // one live-sample count per batch, zero for a batch an abort leaves out
+    d->cam_live.ensure((size_t)nbatch);
+    HIPCHK(hipMemsetAsync(d->cam_live.p, 0, (size_t)nbatch * sizeof(unsigned long long), d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+  }
   Batch Bp[kPipes];
   bind_pipes(d, p, fp, Bp);
   std::vector<Timed> timed;

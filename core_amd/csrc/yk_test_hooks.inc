@@ -98,7 +98,47 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   o[8] = pdf;
 }
 
+// yk_debug_camera_rays: cam_shoot of the bound camera's kind, the function
+// k_camera calls, on host-supplied film positions and lens samples
+template <int KIND>
+__global__ void k_camera_probe(const float* in, long long n, yk_ray* rays, float* wt) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  yk_ray r;
+  wt[i] = cam_shoot<KIND>(in[4 * i], in[4 * i + 1], in[4 * i + 2], in[4 * i + 3], r);
+  rays[i] = r;
+}
+
 }  // namespace
+
+extern "C" int yk_debug_camera_rays(yk_device* d, const float* pxy_lens, int64_t n, yk_ray* rays_out, float* wt_out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_camera_rays: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !pxy_lens || !rays_out || !wt_out || n < 0 || n > (1ll << 24))
+    return set_error(YK_ERR_ARG, "yk_debug_camera_rays: bad arguments");
+  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_camera_rays: no scene uploaded");
+  if (n == 0) return YK_OK;
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  bind_constants(d);
+  DBuf<float> din, dwt;
+  DBuf<yk_ray> drays;
+  din.ensure((size_t)n * 4);
+  dwt.ensure((size_t)n);
+  drays.ensure((size_t)n);
+  HIPCHK(hipMemcpy(din.p, pxy_lens, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
+  auto* kernel = d->cam_host.kind == YK_CAMERA_ORTHOGRAPHIC ? k_camera_probe<YK_CAMERA_ORTHOGRAPHIC>
+                 : d->cam_host.kind == YK_CAMERA_ANGULAR    ? k_camera_probe<YK_CAMERA_ANGULAR>
+                                                            : k_camera_probe<YK_CAMERA_PERSPECTIVE>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, d->stream, (const float*)din.p, (long long)n, drays.p,
+                     dwt.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(rays_out, drays.p, (size_t)n * sizeof(yk_ray), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(wt_out, dwt.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
 
 extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t fn, const float* in, int64_t n,
                                     float* out) {

@@ -103,6 +103,10 @@ typedef struct yk_light {
 enum { YK_BOKEH_DISK1 = 0, YK_BOKEH_DISK2 = 1, YK_BOKEH_TRI = 3, YK_BOKEH_SQR = 4, YK_BOKEH_PENTA = 5,
        YK_BOKEH_HEXA = 6, YK_BOKEH_RING = 7 };
 enum { YK_BOKEH_BIAS_NONE = 0, YK_BOKEH_BIAS_CENTER = 1, YK_BOKEH_BIAS_EDGE = 2 };
+/* the reference's four cameras (src/cameras/): architect is perspectiveCam_t
+ * with its own setAxis; orthographic and angular derive from camera_t and
+ * have no lens (sampleLense() is false) */
+enum { YK_CAMERA_PERSPECTIVE = 0, YK_CAMERA_ARCHITECT = 1, YK_CAMERA_ORTHOGRAPHIC = 2, YK_CAMERA_ANGULAR = 3 };
 typedef struct yk_camera { /* perspectiveCam_t::factory, perspectiveCamera.cc:191-232 */
   float from[3], to[3], up[3];
   int32_t resx, resy;
@@ -112,6 +116,24 @@ typedef struct yk_camera { /* perspectiveCam_t::factory, perspectiveCamera.cc:19
   float aperture, dof_distance;
   int32_t bokeh_type, bokeh_bias;
   float bokeh_rotation;
+  /* Appended fields only: the offsets above are what earlier callers compiled
+   * against, and a zero-initialised tail is the perspective camera.
+   * architect: architectCam_t::factory (architectCamera.cc:94-135), the
+   * perspective parameters. orthographic: orthoCam_t::factory
+   * (orthographicCamera.cc:83-103), "scale" [1]. angular: angularCam_t::factory
+   * (angularCamera.cc:73-101), "angle" [90, degrees], "max_angle" [= angle],
+   * "circular" [1], "mirrored" [0]; a zero-initialised struct must set them.
+   * Those two factories hold aspect, scale, angle and max_angle as double:
+   * aspect and scale only pass through a PFLOAT constructor argument
+   * (aspect_ratio above is that float), max_r = max_angle / angle is a double
+   * division. No aperture on an orthographic or angular camera (YK_ERR_ARG). */
+  int32_t type;     /* YK_CAMERA_* */
+  int32_t circular; /* angular: samples with radius > max_r carry no ray (wt = 0) */
+  int32_t mirrored; /* angular: vright = -camX */
+  int32_t reserved0;
+  double scale;     /* orthographic: finite, > 0 */
+  double angle;     /* angular: finite, > 0 */
+  double max_angle; /* angular: finite, >= 0 */
 } yk_camera;
 
 enum { YK_INTEGRATOR_DIRECT = 0, YK_INTEGRATOR_PATH = 1, YK_INTEGRATOR_PHOTON = 2 };
@@ -290,6 +312,10 @@ int yk_scene_set_mesh_base(yk_scene* s, int32_t obj_id);
  * are flattened with the reference's vertex / normal transform arithmetic. */
 int yk_scene_add_instance(yk_scene* s, int32_t base_obj_id, const float* obj_to_world, int32_t* obj_id_out);
 int yk_scene_add_light(yk_scene* s, const yk_light* l);
+/* YK_ERR_UNSUPPORTED for an unknown type; YK_ERR_ARG for a non-finite or
+ * non-positive scale (orthographic) or angle (angular), a non-finite or
+ * negative max_angle (angular), and an aperture on an orthographic or angular
+ * camera (they have no lens; the parameter is not silently dropped) */
 int yk_scene_set_camera(yk_scene* s, const yk_camera* c);
 /* scene_t::update: gather prims and build the kd-tree (scene.cc:748-785) */
 int yk_scene_build(yk_scene* s);
@@ -385,7 +411,7 @@ typedef struct yk_sphere_light_state { /* sphereLight_t members after its ctor (
   int32_t samples;
 } yk_sphere_light_state;
 
-typedef struct yk_camera_state { /* perspectiveCam_t after setAxis (perspectiveCamera.cc:57-71) */
+typedef struct yk_camera_state { /* the camera after its ctor and setAxis (perspectiveCamera.cc:57-71) */
   float position[3], vright[3], vup[3], vto[3], cam_z[3];
   float near_p[3], far_p[3]; /* near_plane.p / far_plane.p (camera.h:54-57)            */
   int32_t resx, resy;
@@ -396,6 +422,21 @@ typedef struct yk_camera_state { /* perspectiveCam_t after setAxis (perspectiveC
   float dof_rt[3], dof_up[3];
   int32_t bokeh_type, bokeh_bias;
   float lens_ls[16];
+  /* Appended; all zero for the perspective kind. kind names the shootRay that
+   * runs: YK_CAMERA_PERSPECTIVE also for an architect camera, which differs
+   * from perspectiveCam_t in setAxis alone (vup along (0,0,-1),
+   * architectCamera.cc:54-68) and so in the vectors above, not in kind;
+   * yk_scene_set_camera_state takes YK_CAMERA_ARCHITECT as that kind too.
+   * YK_CAMERA_ORTHOGRAPHIC: position is orthoCam_t::pos (the film's corner),
+   * vto = camZ, vup / vright the pixel steps (orthographicCamera.cc:37-49).
+   * YK_CAMERA_ANGULAR: vright = +-camX, vup = camY, vto = camZ, and
+   * angularCam_t's hor_phi, max_r, circular with camera_t's aspect_ratio
+   * (aspect * resy / resx), which its shootRay multiplies v by. */
+  int32_t kind;
+  float hor_phi;      /* angle * M_PI / 180.f, in double, stored to float */
+  float max_r;        /* max_angle / angle, in double, stored to float     */
+  int32_t circular;
+  float aspect_ratio; /* angular only; 0 otherwise                         */
 } yk_camera_state;
 
 int yk_scene_add_material_state(yk_scene* s, const yk_material_state* m, int32_t* id_out);
@@ -549,8 +590,8 @@ int yk_device_build_tree(yk_device* d, const yk_scene* s, int32_t flags, yk_tree
 int yk_device_export_tree(yk_device* d, uint32_t* nodes, int64_t node_cap, uint32_t* leaf, int64_t leaf_cap,
                           int64_t* nnodes_out, int64_t* nleaf_out);
 /* Test-only hooks (the watchdog's tree damage, the lights' function probe)
- * are declared in yk_test_hooks.h and yk_test_hooks_light.h, not here, and
- * are disabled unless YK_DEBUG_HOOKS=1. */
+ * are declared in yk_test_hooks.h, yk_test_hooks_light.h and
+ * yk_test_hooks_camera.h, not here, and are disabled unless YK_DEBUG_HOOKS=1. */
 
 #ifdef __cplusplus
 }

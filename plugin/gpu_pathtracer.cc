@@ -25,6 +25,9 @@
 #include <core_api/imagefilm.h>
 #include <core_api/scene.h>
 #include <core_api/tiledintegrator.h>
+#include <cameras/angularCamera.h>
+#include <cameras/architectCamera.h>
+#include <cameras/orthographicCamera.h>
 #include <cameras/perspectiveCamera.h>
 #include <lights/arealight.h>
 #include <materials/shinydiff.h>
@@ -135,6 +138,11 @@ YK_MEMBER(CamDofUp, perspectiveCam_t, vector3d_t, dof_up)
 YK_MEMBER(CamBokeh, perspectiveCam_t, perspectiveCam_t::bokehType, bkhtype)
 YK_MEMBER(CamBokehBias, perspectiveCam_t, perspectiveCam_t::bkhBiasType, bkhbias)
 YK_MEMBER(CamLS, perspectiveCam_t, std::vector<PFLOAT>, LS)
+YK_MEMBER(CamAspect, camera_t, float, aspect_ratio)
+YK_MEMBER(OrthoPos, orthoCam_t, point3d_t, pos)
+YK_MEMBER(AngHorPhi, angularCam_t, PFLOAT, hor_phi)
+YK_MEMBER(AngMaxR, angularCam_t, PFLOAT, max_r)
+YK_MEMBER(AngCircular, angularCam_t, bool, circular)
 YK_MEMBER(FilmImage, imageFilm_t, rgba2DImage_t*, image)
 YK_MEMBER(FilmCx0, imageFilm_t, int, cx0)
 YK_MEMBER(FilmCy0, imageFilm_t, int, cy0)
@@ -393,11 +401,20 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
       const float rgb[3] = {c.R, c.G, c.B};
       if (yk_scene_set_background(ys, rgb, 1.0f) != YK_OK) return fail();  // color already * power
     }
-    const perspectiveCam_t* cam = dynamic_cast<const perspectiveCam_t*>(scene->getCamera());
-    if (!cam) return unsupported("only the perspective camera runs on the GPU path");
+    // The reference's four cameras, read as the state their constructors,
+    // setAxis and factories left (the angular factory's mirrored vright and
+    // max_r included). architectCam_t is a perspectiveCam_t whose setAxis
+    // differs: its vectors are read like the perspective ones, and its
+    // shootRay is the inherited one.
+    const camera_t* live_cam = scene->getCamera();
+    const perspectiveCam_t* cam = dynamic_cast<const perspectiveCam_t*>(live_cam);
+    const orthoCam_t* ocam = dynamic_cast<const orthoCam_t*>(live_cam);
+    const angularCam_t* acam = dynamic_cast<const angularCam_t*>(live_cam);
+    if (!cam && !ocam && !acam)
+      return unsupported("only the perspective, architect, orthographic and angular cameras run on the GPU path");
     yk_camera_state cs{};
-    const camera_t& cb = *cam;
-    const point3d_t& pos = GET(cb, CamPos);
+    const camera_t& cb = *live_cam;
+    const point3d_t& pos = ocam ? GET(*ocam, OrthoPos) : GET(cb, CamPos);  // orthoCam_t shoots from its own pos
     const vector3d_t &z = GET(cb, CamZ), &vto = GET(cb, CamVto), &vup = GET(cb, CamVup),
                      &vr = GET(cb, CamVright);
     put3(cs.position, pos.x, pos.y, pos.z);
@@ -408,21 +425,32 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
     const vector3d_t &np = GET(cb, CamNear).p, &fp = GET(cb, CamFar).p;
     put3(cs.near_p, np.x, np.y, np.z);
     put3(cs.far_p, fp.x, fp.y, fp.z);
-    cs.resx = cam->resX();
-    cs.resy = cam->resY();
-    // depth of field: the lens state the constructor and setAxis computed
-    // (perspectiveCamera.cc:29-71); libyk samples it as renderTile does
-    const perspectiveCam_t& pc = *cam;
-    cs.aperture = GET(pc, CamAperture);
-    cs.dof_distance = GET(pc, CamDofDistance);
-    const vector3d_t &drt = GET(pc, CamDofRt), &dup = GET(pc, CamDofUp);
-    put3(cs.dof_rt, drt.x, drt.y, drt.z);
-    put3(cs.dof_up, dup.x, dup.y, dup.z);
-    cs.bokeh_type = (int32_t)GET(pc, CamBokeh);
-    cs.bokeh_bias = (int32_t)GET(pc, CamBokehBias);
-    const std::vector<PFLOAT>& ls = GET(pc, CamLS);
-    if (ls.size() > 16) return unsupported("bokeh polygon table larger than 16 entries");
-    for (size_t i = 0; i < ls.size(); ++i) cs.lens_ls[i] = ls[i];
+    cs.resx = live_cam->resX();
+    cs.resy = live_cam->resY();
+    if (cam) {
+      // depth of field: the lens state the constructor and setAxis computed
+      // (perspectiveCamera.cc:29-71); libyk samples it as renderTile does
+      const perspectiveCam_t& pc = *cam;
+      cs.kind = dynamic_cast<const architectCam_t*>(cam) ? YK_CAMERA_ARCHITECT : YK_CAMERA_PERSPECTIVE;
+      cs.aperture = GET(pc, CamAperture);
+      cs.dof_distance = GET(pc, CamDofDistance);
+      const vector3d_t &drt = GET(pc, CamDofRt), &dup = GET(pc, CamDofUp);
+      put3(cs.dof_rt, drt.x, drt.y, drt.z);
+      put3(cs.dof_up, dup.x, dup.y, dup.z);
+      cs.bokeh_type = (int32_t)GET(pc, CamBokeh);
+      cs.bokeh_bias = (int32_t)GET(pc, CamBokehBias);
+      const std::vector<PFLOAT>& ls = GET(pc, CamLS);
+      if (ls.size() > 16) return unsupported("bokeh polygon table larger than 16 entries");
+      for (size_t i = 0; i < ls.size(); ++i) cs.lens_ls[i] = ls[i];
+    } else if (ocam) {
+      cs.kind = YK_CAMERA_ORTHOGRAPHIC;
+    } else {
+      cs.kind = YK_CAMERA_ANGULAR;
+      cs.hor_phi = GET(*acam, AngHorPhi);
+      cs.max_r = GET(*acam, AngMaxR);
+      cs.circular = GET(*acam, AngCircular) ? 1 : 0;
+      cs.aspect_ratio = GET(cb, CamAspect);
+    }
     if (yk_scene_set_camera_state(ys, &cs) != YK_OK) return fail();
     // the empty volume integrator leaves integrate()'s colour as is
     // (pathtracer.cc:323-328 with transmittance 1, integrate 0)
