@@ -264,6 +264,9 @@ SIGNATURES = {
     "yk_debug_shadow_form": (C.c_int, [P, C.POINTER(yk_render_params), C.POINTER(C.c_int32)]),
     "yk_debug_batch_plan": (C.c_int, [C.POINTER(yk_batch_plan_in), C.POINTER(yk_batch_plan)]),
     "yk_debug_last_plan": (C.c_int, [P, C.POINTER(yk_last_plan)]),
+    # include/yk_test_hooks_film.h
+    "yk_debug_film_splat": (C.c_int, [P, C.POINTER(yk_render_params), i32, i32, i32, i32, P, fp, fp, i64, fp]),
+    "yk_debug_aa_flags": (C.c_int, [P, fp, i32, i32, C.c_float, P]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@
 #include "../../include/yk_test_hooks.h"
 #include "../../include/yk_test_hooks_light.h"
 #include "../../include/yk_test_hooks_camera.h"
+#include "../../include/yk_test_hooks_film.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"
@@ -5312,6 +5313,6 @@ int yk_film_filter_from_table(const float* table, float filterw, yk_render_param
 
 #include "yk_photon_host.inc"
 #include "yk_kdtree_gpu.inc"
-#include "yk_test_hooks.inc"
-
 #include "yk_render_host.inc"
+
+#include "yk_test_hooks.inc"

@@ -18,6 +18,27 @@ bool needs_photon_maps(const yk_render_params* p) {
          (p->integrator == YK_INTEGRATOR_DIRECT && p->dl_caustics != 0);
 }
 
+// Tile size, tile count and a custom tile order of the render area (width and
+// height checked before); YK_OK or the error set.
+int check_tiles(const yk_render_params* p) {
+  const int tile = p->tile_size > 0 ? p->tile_size : 32;  // make_film
+  if (tile > 4096) return set_error(YK_ERR_UNSUPPORTED, "tile_size > 4096");
+  const int ntiles = ((p->width + tile - 1) / tile) * ((p->height + tile - 1) / tile);
+  if (ntiles >= (1 << 19)) return set_error(YK_ERR_UNSUPPORTED, "too many tiles");
+  if (p->tile_order && p->tile_order_len > 0) {
+    if (p->tile_order_len != ntiles)
+      return set_error(YK_ERR_ARG, "tile_order must list every tile of the render area once");
+    std::vector<char> seen((size_t)ntiles, 0);
+    for (int i = 0; i < ntiles; ++i) {
+      const int t = p->tile_order[i];
+      if (t < 0 || t >= ntiles || seen[(size_t)t])
+        return set_error(YK_ERR_ARG, "tile_order is not a permutation of the tiles");
+      seen[(size_t)t] = 1;
+    }
+  }
+  return YK_OK;
+}
+
 // Every argument and state check of a render pass; YK_OK or the error set.
 int check_render_params(const yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards,
                         const float* d_film, const PassSpec& ps) {
@@ -47,21 +68,7 @@ int check_render_params(const yk_device* d, const yk_render_params* p, int32_t s
   if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
   if (p->filter_width != 0.f && !(p->filter_width >= 0.501f && p->filter_width <= 4.f))
     return set_error(YK_ERR_ARG, "filter_width must be 0 or in [0.501, 4]");
-  const int tile = p->tile_size > 0 ? p->tile_size : 32;  // make_film
-  if (tile > 4096) return set_error(YK_ERR_UNSUPPORTED, "tile_size > 4096");
-  const int ntiles = ((p->width + tile - 1) / tile) * ((p->height + tile - 1) / tile);
-  if (ntiles >= (1 << 19)) return set_error(YK_ERR_UNSUPPORTED, "too many tiles");
-  if (p->tile_order && p->tile_order_len > 0) {
-    if (p->tile_order_len != ntiles)
-      return set_error(YK_ERR_ARG, "tile_order must list every tile of the render area once");
-    std::vector<char> seen((size_t)ntiles, 0);
-    for (int i = 0; i < ntiles; ++i) {
-      const int t = p->tile_order[i];
-      if (t < 0 || t >= ntiles || seen[(size_t)t])
-        return set_error(YK_ERR_ARG, "tile_order is not a permutation of the tiles");
-      seen[(size_t)t] = 1;
-    }
-  }
+  if (const int rc = check_tiles(p)) return rc;
   // transparent shadows: the device keeps the filtered-prim set of a shadow
   // ray in 9 registers, so at most 8 transparent surfaces (defaults 4-5)
   if (p->transp_shadows && (p->shadow_depth < 0 || p->shadow_depth > 8))
@@ -71,19 +78,9 @@ int check_render_params(const yk_device* d, const yk_render_params* p, int32_t s
   return YK_OK;
 }
 
-// Everything one pass decides on the host before it enqueues: constants, the
-// batch plan and the tile lists of all batches (build_frame_plan; no device
-// state is touched, checked parameters are assumed).
-struct FramePlan {
-  bool pm, cmap, ao, path, merged, split;
-  FilmConst F;
-  RenderConst R;
-  AOConst AOC;
-  PMConst PMC;
-  int K;                    // shadow slots per shading point: the lights', then the AO rays' (gen_ao)
-  int bounces, nsub;        // trace depths and sub-paths (gather paths) of the bounce loop
-  int spec_levels;          // specular recursion: the node store holds min(raydepth, 19) levels (plan_batches)
-  yk_batch_plan plan;
+// The film's side of a pass: which tiles the shard owns and, per batch, the
+// tiles, sample offsets and flagged pixels (owned_tiles, build_tile_lists).
+struct TileLists {
   std::vector<int> owned;   // the shard's tiles in the order the film hands them out
   std::vector<int> rank_of; // custom order: tile -> rank in `owned`, -1 other shards' tiles
   // tile lists of all batches
@@ -94,6 +91,102 @@ struct FramePlan {
   // the film-pixel -> batch-local first sample map the gather reads
   std::vector<int> pix, pmap;
   std::vector<size_t> pix_off;
+};
+
+// The tiles of shard F.shard in the order the film hands them out: row-major,
+// or the custom order's (a checked permutation of the film's tiles).
+void owned_tiles(const FilmConst& F, const int32_t* tile_order, int tile_order_len, TileLists& L) {
+  const int ntiles = F.ntx * ((F.h + F.tile - 1) / F.tile);
+  if (tile_order && tile_order_len > 0) {
+    L.rank_of.assign((size_t)ntiles, -1);
+    for (int i = 0; i < ntiles; ++i) {
+      const int t = tile_order[i];
+      if (t % F.nshards != F.shard) continue;
+      L.rank_of[(size_t)t] = (int)L.owned.size();
+      L.owned.push_back(t);
+    }
+  } else {
+    for (int t = F.shard; t < ntiles; t += F.nshards) L.owned.push_back(t);
+  }
+}
+
+// The lists of nbatch batches of tpb owned tiles each, spp samples per pixel;
+// flags (film-local bytes) restricts the samples to the flagged pixels.
+void build_tile_lists(const FilmConst& F, int nbatch, int tpb, int spp, const uint8_t* flags, TileLists& L) {
+  L.base.assign((size_t)nbatch * (tpb + 1), 0);
+  L.nc_of.assign(nbatch, 0);
+  L.rect_of.resize(nbatch);
+  L.pix_off.assign(nbatch, 0);
+  if (flags) L.pmap.assign((size_t)F.w * F.h, -1);
+  for (int bi = 0; bi < nbatch; ++bi) {
+    const size_t tb0 = (size_t)bi * tpb, tb1 = std::min(L.owned.size(), tb0 + (size_t)tpb);
+    long long nc = 0;
+    int rx0 = 1 << 30, ry0 = 1 << 30, rx1 = -(1 << 30), ry1 = -(1 << 30);
+    L.pix_off[bi] = L.pix.size();
+    for (size_t k = tb0; k < tb1; ++k) {
+      const int t = L.owned[k];
+      const int X = F.cx0 + (t % F.ntx) * F.tile, Y = F.cy0 + (t / F.ntx) * F.tile;
+      const int W = std::min(F.tile, F.cx1 - X), H = std::min(F.tile, F.cy1 - Y);
+      L.tiles.push_back(make_int4(X, Y, W, H));
+      L.base[(size_t)bi * (tpb + 1) + (k - tb0)] = (int)nc;
+      if (flags) {
+        for (int yy = Y; yy < Y + H; ++yy)
+          for (int xx = X; xx < X + W; ++xx) {
+            const size_t px = (size_t)(yy - F.cy0) * F.w + (xx - F.cx0);
+            if (!flags[px]) continue;
+            L.pmap[px] = (int)nc;
+            L.pix.push_back((yy << 16) | xx);
+            nc += spp;
+          }
+      } else {
+        nc += (long long)W * H * spp;
+      }
+      rx0 = std::min(rx0, X);
+      ry0 = std::min(ry0, Y);
+      rx1 = std::max(rx1, X + W);
+      ry1 = std::max(ry1, Y + H);
+    }
+    L.base[(size_t)bi * (tpb + 1) + (tb1 - tb0)] = (int)nc;
+    L.nc_of[bi] = nc;
+    L.rect_of[bi] = make_int4(rx0, ry0, rx1, ry1);
+  }
+}
+
+// The film gather of one batch on `stream`: owned tile ranks [tb0, tb1) with
+// nc samples (colours, in-pixel positions, per-tile sample offsets `base`)
+// into d_film; rect is the batch's tile bounds, pmap the adaptive pass's
+// film-pixel map or null, pext scratch of one entry per pixel slot.
+void launch_film_gather(hipStream_t stream, const FilmConst& F, const int* pmap, int tb0, int tb1, int4 rect,
+                        long long nc, const float4* samples, const float2* sxy, const int* base, char4* pext,
+                        float* d_film) {
+  FilmConst Fb = F;
+  Fb.pmap = pmap;
+  Fb.tb0 = tb0;
+  Fb.tb1 = tb1;
+  const int gx0 = std::max(F.cx0, rect.x + F.olo_x), gy0 = std::max(F.cy0, rect.y + F.olo_y);
+  const int gx1 = std::min(F.cx1, rect.z + F.ohi_x), gy1 = std::min(F.cy1, rect.w + F.ohi_y);
+  const int gw = gx1 - gx0, gh = gy1 - gy0;
+  if (nc > 0 && gw > 0 && gh > 0) {
+    const long long npix = nc / F.spp;  // the batch's pixel slots (spp samples each)
+    launch(k_pixel_extent, grid_for(npix * 64), 256, 0, stream, Fb, sxy, pext, npix);
+    launch(k_film_gather, grid_for((long long)gw * gh), 256, 0, stream, Fb, samples, sxy, base, pext, d_film, gx0, gy0,
+           gw, gh);
+  }
+}
+
+// Everything one pass decides on the host before it enqueues: constants, the
+// batch plan and the tile lists of all batches (build_frame_plan; no device
+// state is touched, checked parameters are assumed).
+struct FramePlan : TileLists {
+  bool pm, cmap, ao, path, merged, split;
+  FilmConst F;
+  RenderConst R;
+  AOConst AOC;
+  PMConst PMC;
+  int K;                    // shadow slots per shading point: the lights', then the AO rays' (gen_ao)
+  int bounces, nsub;        // trace depths and sub-paths (gather paths) of the bounce loop
+  int spec_levels;          // specular recursion: the node store holds min(raydepth, 19) levels (plan_batches)
+  yk_batch_plan plan;
   // per-pipe device words: [0, 2 kAccWords) accumulators {closest nodes,
   // tris, errors, rays; any-hit ...}; then per batch: queue-count words
   // (isub, depth), the final gather's lookup-queue counts (isub, depth) and
@@ -122,18 +215,7 @@ const char* build_frame_plan(const yk_device* d, const yk_render_params* p, int3
   F.d1 = (float)(1.0 / (double)(float)ps.n);
   F.rank_of = nullptr;
   const int spp = F.spp;
-  const int ntiles = F.ntx * ((p->height + F.tile - 1) / F.tile);
-  if (p->tile_order && p->tile_order_len > 0) {
-    fp.rank_of.assign((size_t)ntiles, -1);
-    for (int i = 0; i < ntiles; ++i) {
-      const int t = p->tile_order[i];
-      if (t % nshards != shard) continue;
-      fp.rank_of[(size_t)t] = (int)fp.owned.size();
-      fp.owned.push_back(t);
-    }
-  } else {
-    for (int t = shard; t < ntiles; t += nshards) fp.owned.push_back(t);
-  }
+  owned_tiles(F, p->tile_order, p->tile_order_len, fp);
   RenderConst& R = fp.R;
   R = RenderConst{};
   R.spp = spp;
@@ -209,44 +291,7 @@ const char* build_frame_plan(const yk_device* d, const yk_render_params* p, int3
   fp.launches_per_batch = 2 + 2 * fp.nsub * fp.bounces + (R.pm_fg ? fp.nsub * fp.bounces : 0);
   fp.words_per_batch = 2ll * fp.qwords_per_batch + 128ll * fp.launches_per_batch;
 
-  const int nbatch = fp.plan.nbatch, tpb = fp.plan.tiles_per_batch;
-  fp.base.assign((size_t)nbatch * (tpb + 1), 0);
-  fp.nc_of.assign(nbatch, 0);
-  fp.rect_of.resize(nbatch);
-  fp.pix_off.assign(nbatch, 0);
-  if (ps.flags) fp.pmap.assign((size_t)F.w * F.h, -1);
-  for (int bi = 0; bi < nbatch; ++bi) {
-    const size_t tb0 = (size_t)bi * tpb, tb1 = std::min(fp.owned.size(), tb0 + (size_t)tpb);
-    long long nc = 0;
-    int rx0 = 1 << 30, ry0 = 1 << 30, rx1 = -(1 << 30), ry1 = -(1 << 30);
-    fp.pix_off[bi] = fp.pix.size();
-    for (size_t k = tb0; k < tb1; ++k) {
-      const int t = fp.owned[k];
-      const int X = F.cx0 + (t % F.ntx) * F.tile, Y = F.cy0 + (t / F.ntx) * F.tile;
-      const int W = std::min(F.tile, F.cx1 - X), H = std::min(F.tile, F.cy1 - Y);
-      fp.tiles.push_back(make_int4(X, Y, W, H));
-      fp.base[(size_t)bi * (tpb + 1) + (k - tb0)] = (int)nc;
-      if (ps.flags) {
-        for (int yy = Y; yy < Y + H; ++yy)
-          for (int xx = X; xx < X + W; ++xx) {
-            const size_t px = (size_t)(yy - F.cy0) * F.w + (xx - F.cx0);
-            if (!ps.flags[px]) continue;
-            fp.pmap[px] = (int)nc;
-            fp.pix.push_back((yy << 16) | xx);
-            nc += spp;
-          }
-      } else {
-        nc += (long long)W * H * spp;
-      }
-      rx0 = std::min(rx0, X);
-      ry0 = std::min(ry0, Y);
-      rx1 = std::max(rx1, X + W);
-      ry1 = std::max(ry1, Y + H);
-    }
-    fp.base[(size_t)bi * (tpb + 1) + (tb1 - tb0)] = (int)nc;
-    fp.nc_of[bi] = nc;
-    fp.rect_of[bi] = make_int4(rx0, ry0, rx1, ry1);
-  }
+  build_tile_lists(F, fp.plan.nbatch, fp.plan.tiles_per_batch, spp, ps.flags, fp);
   return nullptr;
 }
 
@@ -540,20 +585,8 @@ int enqueue_batch(BatchCtx& c, int bi) {
   // film: in batch order (tile order), whichever pipe ran the batch; an
   // empty batch keeps the chain of gather events
   if (bi > 0) HIPCHK(hipStreamWaitEvent(P.stream, d->gather_ev[(bi - 1) % kPipes], 0));
-  FilmConst Fb = F;
-  Fb.pmap = c.ps->flags ? d->pmap_dev.p : nullptr;
-  Fb.tb0 = tb0;
-  Fb.tb1 = tb1;
-  const int4 rc = fp.rect_of[bi];
-  const int gx0 = std::max(F.cx0, rc.x + F.olo_x), gy0 = std::max(F.cy0, rc.y + F.olo_y);
-  const int gx1 = std::min(F.cx1, rc.z + F.ohi_x), gy1 = std::min(F.cy1, rc.w + F.ohi_y);
-  const int gw = gx1 - gx0, gh = gy1 - gy0;
-  if (nc > 0 && gw > 0 && gh > 0) {
-    const long long npix = nc / F.spp;  // the batch's pixel slots (spp samples each)
-    launch(k_pixel_extent, grid_for(npix * 64), 256, 0, P.stream, Fb, B.sxy, B.pext, npix);
-    launch(k_film_gather, grid_for((long long)gw * gh), 256, 0, P.stream, Fb, B.samples, B.sxy, TL.base, B.pext,
-           c.d_film, gx0, gy0, gw, gh);
-  }
+  launch_film_gather(P.stream, F, c.ps->flags ? d->pmap_dev.p : nullptr, tb0, tb1, fp.rect_of[bi], nc, B.samples, B.sxy,
+                     TL.base, B.pext, c.d_film);
   HIPCHK(hipEventRecord(d->gather_ev[bi % kPipes], P.stream));
   return YK_OK;
 }

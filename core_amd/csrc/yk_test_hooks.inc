@@ -263,3 +263,114 @@ extern "C" int yk_debug_last_plan(yk_device* d, yk_last_plan* out) {
   out->batch_bytes = d->pipe[0].batch_bytes();
   return YK_OK;
 }
+
+// yk_debug_film_splat: host samples through the renderer's tile lists
+// (owned_tiles, build_tile_lists) and its gather launch (launch_film_gather),
+// in buffers of the call's own.
+extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, int32_t spp,
+                                   int32_t tiles_per_batch, const uint8_t* flags, const float* colours,
+                                   const float* offsets, int64_t n, float* film) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_film_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !p || !film || n < 0 || n > (1ll << 24) || (n > 0 && (!colours || !offsets)) || nshards < 1 || shard < 0 ||
+      shard >= nshards || spp < 1)
+    return set_error(YK_ERR_ARG, "yk_debug_film_splat: bad arguments");
+  if (p->width <= 0 || p->height <= 0 || (long long)p->width * p->height > (1ll << 24))
+    return set_error(YK_ERR_ARG, "yk_debug_film_splat: empty or too large render area");
+  if (p->filter < YK_FILTER_BOX || p->filter > YK_FILTER_LANCZOS) return set_error(YK_ERR_ARG, "unknown filter");
+  if (!std::isfinite(p->aa_pixelwidth) ||
+      (p->filter_width != 0.f && !(p->filter_width >= 0.501f && p->filter_width <= 4.f)))
+    return set_error(YK_ERR_ARG, "aa_pixelwidth must be finite, filter_width 0 or in [0.501, 4]");
+  if (const int rc = check_tiles(p)) return rc;
+  if (flags && (p->xstart + p->width > 65535 || p->ystart + p->height > 65535))
+    return set_error(YK_ERR_UNSUPPORTED, "adaptive passes need coordinates < 65536");
+  for (int64_t i = 0; i < 2 * n; ++i)
+    if (!(offsets[i] >= 0.f && offsets[i] < 1.f))
+      return set_error(YK_ERR_ARG, "yk_debug_film_splat: a sample offset outside [0, 1)");
+  YK_GUARD_BEGIN
+  FilmConst F = make_film(p);
+  F.shard = shard;
+  F.nshards = nshards;
+  F.spp = spp;
+  F.d1 = (float)(1.0 / (double)(float)spp);
+  F.rank_of = nullptr;
+  TileLists L;
+  owned_tiles(F, p->tile_order, p->tile_order_len, L);
+  const int tpb = tiles_per_batch > 0 ? tiles_per_batch : std::max(1, (int)L.owned.size());
+  const int nbatch = (int)((L.owned.size() + (size_t)tpb - 1) / (size_t)tpb);
+  build_tile_lists(F, nbatch, tpb, spp, flags, L);
+  long long total = 0, maxnc = 1;
+  for (const long long nc : L.nc_of) {
+    total += nc;
+    maxnc = std::max(maxnc, nc);
+  }
+  if (total != n) return set_error(YK_ERR_ARG, "yk_debug_film_splat: n is not the sample count of the tile lists");
+  HIPCHK(hipSetDevice(d->ordinal));
+  const size_t nfl = (size_t)F.w * F.h * 5;
+  DBuf<float> dfilm;
+  DBuf<float4> dcol;
+  DBuf<float2> dxy;
+  DBuf<char4> dext;
+  DBuf<int> dbase, dpmap, drank;
+  dfilm.ensure(nfl);
+  dcol.ensure((size_t)maxnc);
+  dxy.ensure((size_t)maxnc);
+  dext.ensure((size_t)maxnc);  // one per pixel slot; maxnc bounds the slots of any spp
+  dbase.ensure(std::max<size_t>(1, L.base.size()));
+  HIPCHK(hipMemcpy(dfilm.p, film, nfl * sizeof(float), hipMemcpyHostToDevice));
+  if (!L.base.empty()) HIPCHK(hipMemcpy(dbase.p, L.base.data(), L.base.size() * sizeof(int), hipMemcpyHostToDevice));
+  if (!L.pmap.empty()) {
+    dpmap.ensure(L.pmap.size());
+    HIPCHK(hipMemcpy(dpmap.p, L.pmap.data(), L.pmap.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (!L.rank_of.empty()) {
+    drank.ensure(L.rank_of.size());
+    HIPCHK(hipMemcpy(drank.p, L.rank_of.data(), L.rank_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    F.rank_of = drank.p;
+  }
+  long long at = 0;
+  for (int bi = 0; bi < nbatch; ++bi) {
+    const long long nc = L.nc_of[bi];
+    const int tb0 = bi * tpb, tb1 = (int)std::min<size_t>(L.owned.size(), (size_t)(bi + 1) * tpb);
+    if (nc > 0) {
+      // the batch's buffers are reused: the copies wait for the previous gather
+      HIPCHK(hipStreamSynchronize(d->stream));
+      HIPCHK(hipMemcpy(dcol.p, colours + 4 * at, (size_t)nc * sizeof(float4), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dxy.p, offsets + 2 * at, (size_t)nc * sizeof(float2), hipMemcpyHostToDevice));
+    }
+    launch_film_gather(d->stream, F, flags ? dpmap.p : nullptr, tb0, tb1, L.rect_of[bi], nc, dcol.p, dxy.p,
+                       dbase.p + (size_t)bi * (tpb + 1), dext.p, dfilm.p);
+    at += nc;
+  }
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(film, dfilm.p, nfl * sizeof(float), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+// yk_debug_aa_flags: next_pass_flags, the adaptive passes' own path, on an
+// uploaded film. threshold <= 0: no flags exist (doMoreSamples is always
+// true), reported as all ones.
+extern "C" int yk_debug_aa_flags(yk_device* d, const float* film, int32_t w, int32_t h, float threshold,
+                                 uint8_t* flags_out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_aa_flags: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !film || !flags_out || w <= 0 || h <= 0 || (long long)w * h > (1ll << 24))
+    return set_error(YK_ERR_ARG, "yk_debug_aa_flags: bad arguments");
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  const size_t npx = (size_t)w * h;
+  DBuf<float> dfilm;
+  dfilm.ensure(npx * 5);
+  HIPCHK(hipMemcpy(dfilm.p, film, npx * 5 * sizeof(float), hipMemcpyHostToDevice));
+  yk_render_params q{};
+  q.width = w;
+  q.height = h;
+  q.aa_threshold = threshold;
+  std::vector<uint8_t> host_flags;
+  const uint8_t* fl = next_pass_flags(d, dfilm.p, &q, host_flags);
+  if (fl) std::memcpy(flags_out, fl, npx);
+  else std::memset(flags_out, 1, npx);
+  return YK_OK;
+  YK_GUARD_END
+}

@@ -29,9 +29,11 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert hooks == ["yk_debug_batch_plan", "yk_debug_last_plan", "yk_debug_qmc_probe", "yk_debug_shading_kind",
                      "yk_debug_shadow_form", "yk_debug_small_scene", "yk_device_debug_set_node"] \
         and not set(hooks) & set(names)
-    for n in hooks:
+    film_hooks = declared_functions("yk_test_hooks_film.h")
+    assert film_hooks == ["yk_debug_aa_flags", "yk_debug_film_splat"] and not set(film_hooks) & set(names)
+    for n in hooks + film_hooks:
         assert hasattr(raw, n) and n in A.SIGNATURES
-    assert set(A.SIGNATURES) <= set(names) | set(hooks)
+    assert set(A.SIGNATURES) <= set(names) | set(hooks) | set(film_hooks)
 
 
 def test_debug_hook_disabled_without_env(monkeypatch):
