@@ -135,7 +135,11 @@ class yk_render_params(C.Structure):
                 ("filter_width", C.c_float), ("tile_order", C.POINTER(C.c_int32)), ("tile_order_len", C.c_int32),
                 # directlighting's own options: ambient occlusion and photon caustics
                 ("do_ao", C.c_int32), ("ao_samples", C.c_int32), ("ao_distance", C.c_float), ("ao_color", f3),
-                ("dl_caustics", C.c_int32)]
+                ("dl_caustics", C.c_int32),
+                # film options: the depth channel, premultiplied alpha, clamp_rgb
+                ("z_channel", C.c_int32), ("normalize_z_channel", C.c_int32), ("depth_min", C.c_float),
+                ("depth_inv_range", C.c_float), ("depth_film", C.c_void_p), ("premult_alpha", C.c_int32),
+                ("clamp_rgb", C.c_int32)]
 
     def copy(self):
         p = yk_render_params()
@@ -250,6 +254,8 @@ SIGNATURES = {
     "yk_trace_shadow_filtered": (C.c_int, [P, P, i64, P, P, i32, C.POINTER(yk_stats)]),
     "yk_render_shard": (C.c_int, [P, C.POINTER(yk_render_params), i32, i32, P, C.POINTER(yk_stats)]),
     "yk_film_resolve": (C.c_int, [P, C.POINTER(yk_render_params), P, P]),
+    "yk_depth_range": (C.c_int, [P, C.POINTER(yk_render_params), fp, fp]),
+    "yk_depth_resolve": (C.c_int, [P, C.POINTER(yk_render_params), P, P]),
     "yk_render_film": (C.c_int, [P, C.POINTER(yk_render_params), i32, i32, fp, C.POINTER(yk_stats)]),
     "yk_render_multi": (C.c_int, [C.POINTER(P), i32, C.POINTER(yk_render_params), fp, C.POINTER(yk_stats)]),
     "yk_render": (C.c_int, [P, C.POINTER(yk_render_params), fp, C.POINTER(yk_stats)]),

@@ -34,6 +34,7 @@
 #include "../../include/yk_test_hooks_light.h"
 #include "../../include/yk_test_hooks_camera.h"
 #include "../../include/yk_test_hooks_film.h"
+#include "../../include/yk_test_hooks_depth.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"
@@ -3720,6 +3721,92 @@ __global__ void __launch_bounds__(256) k_pixel_extent(FilmConst F, const float2*
   if (lane == 0) ext[slot] = make_char4((signed char)x0, (signed char)x1, (signed char)y0, (signed char)y1);
 }
 
+// What a gather adds up, as a policy of the shared walk (film_gather_walk):
+// the sample type, the pixel's sums (loaded from and stored to the film) and
+// the per-contribution arithmetic. GatherColour<false, false> is the film of
+// every render without film options, with the arithmetic the gather has
+// always had; the other instantiations are chosen on the host
+// (launch_film_gather) and cost those renders nothing.
+//
+// CLAMP: colorA_t::clampRGB01 once per sample, on load (imagefilm.cc:457,
+// color.h:119-124; a NaN passes both comparisons and stays). PREMULT:
+// addSample premultiplies its local copy inside the pixel loop (imagefilm.cc:
+// 502), so the m-th pixel of the sample's window, row-major after the clamp
+// to the film area, takes the colour after m sequential RGB *= A.
+template <bool CLAMP, bool PREMULT>
+struct GatherColour {
+  using Sample = float4;
+  static constexpr bool kPremult = PREMULT;
+  static constexpr int kStride = 5;
+  float aR, aG, aB, aA, aW;
+  __device__ __forceinline__ void load(const float* px) {
+    aR = px[0];
+    aG = px[1];
+    aB = px[2];
+    aA = px[3];
+    aW = px[4];
+  }
+  __device__ __forceinline__ void store(float* px) const {
+    px[0] = aR;
+    px[1] = aG;
+    px[2] = aB;
+    px[3] = aA;
+    px[4] = aW;
+  }
+  static __device__ __forceinline__ Sample none() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  static __device__ __forceinline__ Sample fetch(const Sample* __restrict__ s, long long i) {
+    float4 c = s[i];
+    if constexpr (CLAMP) {
+      c.x = c.x < 0.f ? 0.f : (c.x > 1.f ? 1.f : c.x);
+      c.y = c.y < 0.f ? 0.f : (c.y > 1.f ? 1.f : c.y);
+      c.z = c.z < 0.f ? 0.f : (c.z > 1.f ? 1.f : c.z);
+    }
+    return c;
+  }
+  // -> whether the contribution counts
+  __device__ __forceinline__ bool add(float wt, Sample c, int m) {
+    if constexpr (PREMULT) {
+      for (int i = 0; i < m; ++i) {
+        c.x = c.x * c.w;
+        c.y = c.y * c.w;
+        c.z = c.z * c.w;
+      }
+    }
+    aR = aR + wt * c.x;
+    aG = aG + wt * c.y;
+    aB = aB + wt * c.z;
+    aA = aA + wt * c.w;
+    aW = aW + wt;
+    return true;
+  }
+};
+
+// imageFilm_t::addDepthSample (imagefilm.cc:513-564): one colour channel's
+// arithmetic plus the weight, on a film of {val, weight}. A NaN is a sample
+// without a depth value (k_depth_samples): it adds nothing, weight included.
+struct GatherDepth {
+  using Sample = float;
+  static constexpr bool kPremult = false;
+  static constexpr int kStride = 2;
+  float aV, aW;
+  __device__ __forceinline__ void load(const float* px) {
+    aV = px[0];
+    aW = px[1];
+  }
+  __device__ __forceinline__ void store(float* px) const {
+    px[0] = aV;
+    px[1] = aW;
+  }
+  static __device__ __forceinline__ Sample none() { return 0.f; }
+  static __device__ __forceinline__ Sample fetch(const Sample* __restrict__ s, long long i) { return s[i]; }
+  __device__ __forceinline__ bool add(float wt, Sample v, int) {
+    if (v != v) return false;
+    aV = aV + wt * v;
+    aW = aW + wt;
+    return true;
+  }
+};
+
 // imageFilm_t::addSample as a gather (imagefilm.cc:453-511): each thread owns
 // one target pixel and adds every covering sample of the batch in the
 // reference's single-thread order -- tiles in the order the film hands them
@@ -3727,11 +3814,12 @@ __global__ void __launch_bounds__(256) k_pixel_extent(FilmConst F, const float2*
 // so the float sums match the sequential CPU splat bit for bit.
 // Candidate sources are walked in that order directly: the tiles the filter
 // window touches in row-major tile order, inside each its window rows and
-// columns.
-__global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* __restrict__ samples,
-                                                     const float2* __restrict__ sxy, const int* __restrict__ tile_base,
-                                                     const char4* __restrict__ ext, float* __restrict__ film,
-                                                     int rx0, int ry0, int rw, int rh) {
+// columns. The walk is shared by the colour film and the depth film (Acc).
+template <class Acc>
+__device__ __forceinline__ void film_gather_walk(const FilmConst& F, const typename Acc::Sample* __restrict__ samples,
+                                                 const float2* __restrict__ sxy, const int* __restrict__ tile_base,
+                                                 const char4* __restrict__ ext, float* __restrict__ film, int rx0,
+                                                 int ry0, int rw, int rh) {
   const int tid = blockIdx.x * blockDim.x + threadIdx.x;
   if (tid >= rw * rh) return;
   const int tx = rx0 + tid % rw, ty = ry0 + tid / rw;
@@ -3742,8 +3830,9 @@ __global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* 
   if (sx0 > sx1 || sy0 > sy1) return;
   const int tc0 = (sx0 - F.cx0) / F.tile, tc1 = (sx1 - F.cx0) / F.tile;
   const int tr0 = (sy0 - F.cy0) / F.tile, tr1 = (sy1 - F.cy0) / F.tile;
-  float* px = film + 5 * ((size_t)(ty - F.cy0) * F.w + (tx - F.cx0));
-  float aR = px[0], aG = px[1], aB = px[2], aA = px[3], aW = px[4];
+  float* px = film + Acc::kStride * ((size_t)(ty - F.cy0) * F.w + (tx - F.cx0));
+  Acc a;
+  a.load(px);
   bool any = false;
   // one tile of the batch: its source pixels in the window, rows, columns, samples
   auto tile = [&](int tr, int tc, int rank) {
@@ -3777,6 +3866,7 @@ __global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* 
               dd[k] = (s0 + k < F.spp) ? sxy[cbase + s0 + k] : make_float2(-8.f, -8.f);
             float wt[kGatherGroup];
             bool acc[kGatherGroup];
+            int mm[Acc::kPremult ? kGatherGroup : 1];
 #pragma unroll
             for (int k = 0; k < kGatherGroup; ++k) {
               const double dx = dd[k].x, dy = dd[k].y;
@@ -3789,21 +3879,23 @@ __global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* 
                 const int xi = floor2int(fabs(((double)ox - (dx - 0.5)) * F.tableScale));
                 const int yi = floor2int(fabs(((double)oy - (dy - 0.5)) * F.tableScale));
                 wt[k] = F.table[yi * 16 + xi];
+                if constexpr (Acc::kPremult) {
+                  // the target's place in the sample's window after the clamp
+                  // to the film area, row-major from 1 (imagefilm.cc:463-466, 492-502)
+                  const int wx0 = max(F.cx0 - sx, dx0), wx1 = min(F.cx1 - sx - 1, dx1);
+                  const int wy0 = max(F.cy0 - sy, dy0);
+                  mm[k] = (oy - wy0) * (wx1 - wx0 + 1) + (ox - wx0) + 1;
+                }
               }
             }
-            float4 col[kGatherGroup];
+            typename Acc::Sample col[kGatherGroup];
 #pragma unroll
             for (int k = 0; k < kGatherGroup; ++k)
-              col[k] = acc[k] ? samples[cbase + s0 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
+              col[k] = acc[k] ? Acc::fetch(samples, cbase + s0 + k) : Acc::none();
 #pragma unroll
             for (int k = 0; k < kGatherGroup; ++k) {
               if (!acc[k]) continue;
-              aR = aR + wt[k] * col[k].x;
-              aG = aG + wt[k] * col[k].y;
-              aB = aB + wt[k] * col[k].z;
-              aA = aA + wt[k] * col[k].w;
-              aW = aW + wt[k];
-              any = true;
+              if (a.add(wt[k], col[k], Acc::kPremult ? mm[k] : 0)) any = true;
             }
           }
         }
@@ -3838,11 +3930,97 @@ __global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* 
       }
   }
   if (!any) return;
-  px[0] = aR;
-  px[1] = aG;
-  px[2] = aB;
-  px[3] = aA;
-  px[4] = aW;
+  a.store(px);
+}
+
+template <bool CLAMP, bool PREMULT>
+__global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* __restrict__ samples,
+                                                     const float2* __restrict__ sxy, const int* __restrict__ tile_base,
+                                                     const char4* __restrict__ ext, float* __restrict__ film,
+                                                     int rx0, int ry0, int rw, int rh) {
+  film_gather_walk<GatherColour<CLAMP, PREMULT>>(F, samples, sxy, tile_base, ext, film, rx0, ry0, rw, rh);
+}
+
+// The depth film's gather: the same walk over the batch's depth samples.
+__global__ void __launch_bounds__(256) k_depth_gather(FilmConst F, const float* __restrict__ depths,
+                                                      const float2* __restrict__ sxy, const int* __restrict__ tile_base,
+                                                      const char4* __restrict__ ext, float* __restrict__ film,
+                                                      int rx0, int ry0, int rw, int rh) {
+  film_gather_walk<GatherDepth>(F, depths, sxy, tile_base, ext, film, rx0, ry0, rw, rh);
+}
+
+// The depth sample of every camera sample of a batch (renderTile,
+// integrator.cc:313-334), after the batch's primary closest-hit launch:
+// c_ray.tmax is the camera hit's t (scene_t::intersect stores it, scene.cc:
+// 877), on a miss what shootRay left, the far plane's distance. Raw: tmax,
+// 99999997952.f where it is <= 0. Normalised: 1 - (tmax - minDepth) * maxDepth
+// where tmax > 0, else 0 (source order; contraction is off). A sample
+// without a ray (wt = 0, an angular camera's; cam_shoot gives it direction 0)
+// reaches `continue` before this point: NaN, which the gather skips.
+struct DepthConst {
+  int normalize;
+  float dmin, dinv;
+};
+__global__ void __launch_bounds__(256) k_depth_samples(const yk_ray* __restrict__ rays,
+                                                       const yk_hit* __restrict__ hits, float* __restrict__ out,
+                                                       DepthConst D, long long nc) {
+  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const yk_ray r = rays[c];
+  const yk_hit h = hits[c];
+  float depth;
+  if (r.dir[0] == 0.f && r.dir[1] == 0.f && r.dir[2] == 0.f && r.tmin == 0.f && r.tmax == -1.0f) {
+    depth = __int_as_float(0x7fc00000);
+  } else {
+    const float tmax = h.prim >= 0 ? h.t : r.tmax;
+    if (D.normalize) {
+      depth = 0.f;
+      if (tmax > 0.f) depth = 1.f - (tmax - D.dmin) * D.dinv;
+    } else {
+      depth = tmax;
+      if (depth <= 0.f) depth = 99999997952.f;
+    }
+  }
+  out[c] = depth;
+}
+
+// precalcDepths' rays (integrator.cc:116-121): shootRay(i, j, 0.5, 0.5) for
+// i < resY, j < resX -- the row index goes in as px -- in that order.
+template <int KIND>
+__global__ void __launch_bounds__(256) k_depth_range_rays(int resx, int resy, yk_ray* __restrict__ rays) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)resx * resy) return;
+  const int i = (int)(t / resx), j = (int)(t % resx);
+  yk_ray r;
+  cam_shoot<KIND>((float)i, (float)j, 0.5f, 0.5f, r);
+  rays[t] = r;
+}
+
+// precalcDepths' min / max (integrator.cc:122-124) over the traced rays:
+// tmax = the hit's t, else the ray's own. Both are order-independent:
+// maxDepth starts at 0 and minDepth takes only tmax >= 0, so every value
+// that can win is a non-negative float, and those order as their bits do.
+// mm[0]: max bits (from 0), mm[1]: min bits (from 1e38f's).
+__global__ void __launch_bounds__(256) k_depth_range_reduce(const yk_ray* __restrict__ rays,
+                                                            const yk_hit* __restrict__ hits, long long n,
+                                                            unsigned* __restrict__ mm) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned hi = 0u, lo = 0xFFFFFFFFu;
+  if (t < n) {
+    const yk_hit h = hits[t];
+    float tmax = h.prim >= 0 ? h.t : rays[t].tmax;
+    if (tmax == 0.f) tmax = 0.f;  // -0 compares >= 0: its place is +0's
+    if (tmax >= 0.f) hi = lo = (unsigned)__float_as_int(tmax);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
+    lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (hi != 0u) atomicMax(mm, hi);
+    if (lo != 0xFFFFFFFFu) atomicMin(mm + 1, lo);
+  }
 }
 
 // yk_render_multi's reduce: acc = ((f[0] + f[1]) + f[2]) + ... in shard
@@ -3905,8 +4083,9 @@ __global__ void k_aa_flags(const float* __restrict__ film, int w, int h, float t
 }
 
 // imageFilm_t::flush: pixel_t::normalized (colorA_t / f multiplies by 1.0/f,
-// color.h:329-333) + clampRGB0 (imagefilm.cc:400-424)
-__global__ void k_film_resolve(const float* __restrict__ film, float* __restrict__ rgba, long long npx) {
+// color.h:329-333) + clampRGB0 (imagefilm.cc:400-424); premult: the clamped
+// pixel's alphaPremultiply (imagefilm.cc:423)
+__global__ void k_film_resolve(const float* __restrict__ film, float* __restrict__ rgba, long long npx, int premult) {
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= npx) return;
   const float* a = film + 5 * p;
@@ -3918,10 +4097,26 @@ __global__ void k_film_resolve(const float* __restrict__ film, float* __restrict
     b = a[2] * f;
     al = a[3] * f;
   }
-  rgba[4 * p] = r < 0.f ? 0.f : r;
-  rgba[4 * p + 1] = g < 0.f ? 0.f : g;
-  rgba[4 * p + 2] = b < 0.f ? 0.f : b;
+  r = r < 0.f ? 0.f : r;
+  g = g < 0.f ? 0.f : g;
+  b = b < 0.f ? 0.f : b;
+  if (premult) {
+    r = r * al;
+    g = g * al;
+    b = b * al;
+  }
+  rgba[4 * p] = r;
+  rgba[4 * p + 1] = g;
+  rgba[4 * p + 2] = b;
   rgba[4 * p + 3] = al;
+}
+
+// pixelGray_t::normalized (image_buffers.h:50-54): a float division
+__global__ void k_depth_resolve(const float* __restrict__ depth, float* __restrict__ z, long long npx) {
+  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= npx) return;
+  const float v = depth[2 * p], w = depth[2 * p + 1];
+  z[p] = w > 0.f ? v / w : 0.f;
 }
 
 #include "yk_photon.inc"
@@ -4003,6 +4198,7 @@ struct Pipe {
   DBuf<float> fgl, fglen;  // final gathering: lcol (3 per sample) and path length
   DBuf<float4> lkq;        // final gathering: radiance-map lookup queue (point | owner, normal)
   DBuf<float> s_filt, sl_aux;  // transparent shadows
+  DBuf<float> zs;              // z_channel: one depth sample per camera sample (k_depth_samples)
   void create() {
     HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     HIPCHK(hipEventCreate(&ev0));
@@ -4033,7 +4229,7 @@ struct Pipe {
            held(qo1) + held(tile_base) + held(tiles) + held(p_rays) + held(qr0) + held(qr1) + held(s_dir) +
            held(p_hits) + held(qh0) + held(qh1) + held(sl_flags) + held(s_occl) + held(samples) + held(sxy) +
            held(pext) + held(psample) + held(incl) + held(caus) + held(emit0) + held(fgl) + held(fglen) + held(lkq) +
-           held(s_filt) + held(sl_aux);
+           held(s_filt) + held(sl_aux) + held(zs);
   }
   // every device buffer of the pipe
   long long all_bytes() const { return batch_bytes() + held(counters) + held(words) + held(ovf); }
@@ -4160,10 +4356,11 @@ const char* plan_batches(const yk_batch_plan_in& in, yk_batch_plan& out) {
   // the 400 B; 2 B per slot of margin; per region 50 B per slot (32-B ray,
   // contribution, flag, result, queue entry), 34 B + a 16-B origin per sample
   // in the split form; + 32 B of path state per extra region; transparent
-  // shadows add 28 B per slot (s_filt, sl_aux)
   const long long region_bytes = in.split ? 34ll * K + 16 : 50ll * K;
+  // shadows add 28 B per slot (s_filt, sl_aux); z_channel (reserved bit 0)
+  // adds the 4-B depth sample (Pipe::zs)
   const long long bytes_per_sample = 400 + 2ll * K + region_bytes + (long long)(regions - 1) * (region_bytes + 32) +
-                                     (in.transp_shadows ? 28ll * K : 0);
+                                     (in.transp_shadows ? 28ll * K : 0) + ((in.reserved & 1) ? 4 : 0);
   out.bytes_per_sample = bytes_per_sample;
   const long long target_env = in.target_samples > 0 ? in.target_samples : (32ll << 20);
   const long long target =
@@ -4304,12 +4501,19 @@ struct yk_device {
   // memory when another handle on the same GPU uploaded a different scene
   std::vector<DMat> mats_host;
   DCam cam_host{};
+  // what precalcDepths reads of the camera (yk_depth_range): its resolution,
+  // and the clip values when it was set from parameters
+  int cam_resx = 0, cam_resy = 0;
+  bool cam_has_clip = false;
+  float cam_near_clip = 0.f, cam_far_clip = 0.f;
   // yk_render_multi state, kept across calls (no allocation once sized): this
   // device's shard film; as the reducing device, the sum, one staging film per
   // peer GPU and one copy stream + event per peer (each peer's copy drives its
   // own xGMI link)
   DBuf<float> mfilm, macc;
+  DBuf<float> mdepth, mdacc;  // z_channel: this device's shard depth film; the reducing device's sum
   DBuf<float> mstage[kMaxMultiDev];
+  DBuf<float> mdstage[kMaxMultiDev];  // z_channel: a peer GPU's shard depth film
   // the frame plan's tile lists (upload_frame_plan; grow-only, so repeated renders allocate nothing)
   DBuf<int4> tiles_dev;
   DBuf<int> base_dev, pix_dev, pmap_dev, rank_dev;
@@ -5139,6 +5343,11 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   for (int k = 0; k < 3; ++k) d->bg[k] = S.background[k];
   d->mats_host = mats;
   d->cam_host = make_cam(S.camera_state);
+  d->cam_resx = S.camera_state.resx;
+  d->cam_resy = S.camera_state.resy;
+  d->cam_has_clip = S.camera_has_params;
+  d->cam_near_clip = S.camera.near_clip;
+  d->cam_far_clip = S.camera.far_clip;
   d->S.tris = d->tris.p;
   d->S.nodes = d->nodes.p;
   d->S.leaf = d->leaf.p;

@@ -5,6 +5,7 @@ struct PassSpec {
   int n, off;
   bool multipass;
   const uint8_t* flags;
+  float* d_depth = nullptr;  // z_channel: the pass's depth film on the device (p->depth_film may be host memory)
 };
 
 namespace {
@@ -36,6 +37,16 @@ int check_tiles(const yk_render_params* p) {
       seen[(size_t)t] = 1;
     }
   }
+  return YK_OK;
+}
+
+// z_channel's own parameters (the depth film's memory space is the caller's
+// matter); YK_OK or the error set. maxDepth may be inf, as in the reference.
+int check_depth_params(const yk_render_params* p) {
+  if (!p->z_channel) return YK_OK;
+  if (!p->depth_film) return set_error(YK_ERR_ARG, "z_channel needs a depth_film");
+  if (p->normalize_z_channel && !std::isfinite(p->depth_min))
+    return set_error(YK_ERR_ARG, "normalize_z_channel needs a finite depth_min (yk_depth_range)");
   return YK_OK;
 }
 
@@ -75,6 +86,7 @@ int check_render_params(const yk_device* d, const yk_render_params* p, int32_t s
     return set_error(YK_ERR_UNSUPPORTED, "shadowDepth must be in [0, 8] with transpShad");
   if (ps.flags && (p->xstart + p->width > 65535 || p->ystart + p->height > 65535))
     return set_error(YK_ERR_UNSUPPORTED, "adaptive passes need coordinates < 65536");
+  if (const int rc = check_depth_params(p)) return rc;
   return YK_OK;
 }
 
@@ -156,9 +168,17 @@ void build_tile_lists(const FilmConst& F, int nbatch, int tpb, int spp, const ui
 // nc samples (colours, in-pixel positions, per-tile sample offsets `base`)
 // into d_film; rect is the batch's tile bounds, pmap the adaptive pass's
 // film-pixel map or null, pext scratch of one entry per pixel slot.
+// opt: the colour gather's variant (clamp_rgb, premult_alpha; both off is the
+// kernel every other render runs). depths / d_depth: the batch's depth samples
+// and the depth film, or null -- the depth gather reuses the extents.
+struct FilmOptions {
+  bool clamp, premult;
+};
+inline FilmOptions film_options(const yk_render_params* p) { return FilmOptions{p->clamp_rgb != 0, p->premult_alpha != 0}; }
 void launch_film_gather(hipStream_t stream, const FilmConst& F, const int* pmap, int tb0, int tb1, int4 rect,
                         long long nc, const float4* samples, const float2* sxy, const int* base, char4* pext,
-                        float* d_film) {
+                        float* d_film, FilmOptions opt = FilmOptions{false, false}, const float* depths = nullptr,
+                        float* d_depth = nullptr) {
   FilmConst Fb = F;
   Fb.pmap = pmap;
   Fb.tb0 = tb0;
@@ -169,8 +189,14 @@ void launch_film_gather(hipStream_t stream, const FilmConst& F, const int* pmap,
   if (nc > 0 && gw > 0 && gh > 0) {
     const long long npix = nc / F.spp;  // the batch's pixel slots (spp samples each)
     launch(k_pixel_extent, grid_for(npix * 64), 256, 0, stream, Fb, sxy, pext, npix);
-    launch(k_film_gather, grid_for((long long)gw * gh), 256, 0, stream, Fb, samples, sxy, base, pext, d_film, gx0, gy0,
-           gw, gh);
+    auto* gather = opt.clamp ? (opt.premult ? k_film_gather<true, true> : k_film_gather<true, false>)
+                             : (opt.premult ? k_film_gather<false, true> : k_film_gather<false, false>);
+    if (samples)
+      launch(gather, grid_for((long long)gw * gh), 256, 0, stream, Fb, samples, sxy, base, pext, d_film, gx0, gy0, gw,
+             gh);
+    if (depths)
+      launch(k_depth_gather, grid_for((long long)gw * gh), 256, 0, stream, Fb, depths, sxy, base, pext, d_depth, gx0,
+             gy0, gw, gh);
   }
 }
 
@@ -279,6 +305,7 @@ const char* build_frame_plan(const yk_device* d, const yk_render_params* p, int3
   pin.tile = F.tile;
   pin.spp = spp;
   pin.pipes = pipes_env();
+  pin.reserved = p->z_channel ? 1 : 0;  // 4 B per sample of depth samples
   pin.owned_tiles = (long long)fp.owned.size();
   const char* target_env = std::getenv("YK_BATCH_SAMPLES");
   pin.target_samples = target_env ? std::atoll(target_env) : 0;
@@ -324,6 +351,7 @@ void bind_pipes(yk_device* d, const yk_render_params* p, const FramePlan& fp, Ba
     P.words.ensure((size_t)(2 * kAccWords + (d->spec ? 0 : fp.words_per_batch * nb_here)));
     HIPCHK(hipMemsetAsync(P.words.p, 0, P.words.n * sizeof(unsigned long long), P.stream));
     Bp[pi] = P.bind(pl.maxc, fp.K, pl.tiles_per_batch, fp.R.ps != 0, p->transp_shadows != 0, pl.regions, fp.split);
+    if (p->z_channel) P.zs.ensure(pl.maxc);
     if (fp.R.pm_fg) {
       P.fgl.ensure(3 * pl.maxc);
       P.fglen.ensure(pl.maxc);
@@ -385,6 +413,10 @@ struct BatchCtx {
   // the batch's live camera-sample count (d->cam_live), nullptr unless the
   // camera can have samples without a ray (cam_can_die)
   unsigned long long* live = nullptr;
+  // z_channel: the batch's depth samples (the pipe's zs) and what
+  // k_depth_samples computes them with; nullptr otherwise
+  float* zs = nullptr;
+  DepthConst DC{};
 };
 
 unsigned long long* qw(const BatchCtx& c, int isub, int depth) { return c.bw + isub * (c.fp->bounces + 1) + depth; }
@@ -468,6 +500,9 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   // the shadow queue's buffer, which k_shade_primary fills only afterwards)
   if (c.live && node_base == 0) trace(c, true, ray_src(Bc.p_rays), Bc.s_idx, RayCount{c.live, 0, 0}, Bc.p_hits, nullptr);
   else trace(c, true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
+  // z_channel: the camera samples' depth, before the specular recursion's
+  // later generations reuse the hit records
+  if (c.zs && node_base == 0) launch(k_depth_samples, grid_for(n), 256, 0, s, Bc.p_rays, Bc.p_hits, c.zs, c.DC, n);
   launch(shade_primary_fn(d->diff_only, d->xl_lights, fp.ao), grid_for(n, YK_PRIMARY_BLOCK), YK_PRIMARY_BLOCK, 0, s,
          d->S, Bc, Rc, n, qw(c, 0, 0), fp.AOC);
   if (!merged) {
@@ -562,6 +597,7 @@ int enqueue_batch(BatchCtx& c, int bi) {
   const TileList TL{d->tiles_dev.p + (size_t)tb0, d->base_dev.p + (size_t)bi * (tpb + 1), tb1 - tb0,
                     c.ps->flags ? d->pix_dev.p + fp.pix_off[bi] : nullptr};
   c.live = cam_can_die(d) ? d->cam_live.p + bi : nullptr;
+  c.zs = (c.p->z_channel && c.ps->d_depth) ? P.zs.p : nullptr;
   if (nc > 0) {  // else an adaptive pass with nothing to resample in this batch
     // one instantiation per shootRay; a perspective or architect camera runs
     // the first, whose per-sample code is the only one those scenes launch
@@ -586,7 +622,7 @@ int enqueue_batch(BatchCtx& c, int bi) {
   // empty batch keeps the chain of gather events
   if (bi > 0) HIPCHK(hipStreamWaitEvent(P.stream, d->gather_ev[(bi - 1) % kPipes], 0));
   launch_film_gather(P.stream, F, c.ps->flags ? d->pmap_dev.p : nullptr, tb0, tb1, fp.rect_of[bi], nc, B.samples, B.sxy,
-                     TL.base, B.pext, c.d_film);
+                     TL.base, B.pext, c.d_film, film_options(c.p), c.zs, c.ps->d_depth);
   HIPCHK(hipEventRecord(d->gather_ev[bi % kPipes], P.stream));
   return YK_OK;
 }
@@ -664,6 +700,7 @@ int render_pass(yk_device* d, const yk_render_params* p, int32_t shard, int32_t 
   std::vector<Timed> timed;
   size_t evn[kPipes] = {};
   BatchCtx c{d, p, &fp, &ps, d_film, bind_node_store(d, fp), &timed, evn, 0, nullptr, Batch{}, nullptr, 0};
+  c.DC = DepthConst{p->normalize_z_channel ? 1 : 0, p->depth_min, p->depth_inv_range};
   long long samples_total = 0;
   bool aborted = false;
   for (int bi = 0; bi < nbatch; ++bi) {
@@ -717,19 +754,21 @@ int yk_render_shard(yk_device* d, const yk_render_params* p, int32_t shard, int3
     return set_error(YK_ERR_ARG, "yk_render_shard: bad arguments");
   if (p->aa_passes < 1) return set_error(YK_ERR_ARG, "AA_passes must be >= 1");
   const int n0 = std::max(1, p->aa_samples);  // scene_t::setAntialiasing, scene.cc:736-742
-  if (p->aa_passes == 1) return render_pass(d, p, shard, nshards, d_film, st, PassSpec{n0, 0, false, nullptr});
+  float* d_depth = p->z_channel ? p->depth_film : nullptr;  // device memory, as d_film is
+  if (p->aa_passes == 1) return render_pass(d, p, shard, nshards, d_film, st, PassSpec{n0, 0, false, nullptr, d_depth});
   // tiledIntegrator_t::render, integrator.cc:132-170: pass 0 everywhere, then
   // AA_inc_samples more in the pixels imageFilm_t::nextPass flags
   if (nshards != 1)
     return set_error(YK_ERR_UNSUPPORTED, "AA_passes > 1 needs the whole film (nshards = 1): nextPass reads it");
   const int inc = p->aa_inc_samples > 0 ? p->aa_inc_samples : n0;
-  int rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{n0, 0, true, nullptr});
+  int rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{n0, 0, true, nullptr, d_depth});
   if (rc != YK_OK) return rc;  // YK_ERR_ABORTED included: no further passes
   YK_GUARD_BEGIN
   std::vector<uint8_t> flags;
   for (int pass = 1; pass < p->aa_passes; ++pass) {
     const uint8_t* fl = next_pass_flags(d, d_film, p, flags);
-    rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{inc, n0 + (pass - 1) * inc, true, fl});
+    // depth samples land in the resampled pixels alone, as the colour samples do
+    rc = render_pass(d, p, 0, 1, d_film, st, PassSpec{inc, n0 + (pass - 1) * inc, true, fl, d_depth});
     if (rc != YK_OK) return rc;
   }
   return YK_OK;
@@ -741,8 +780,70 @@ int yk_film_resolve(yk_device* d, const yk_render_params* p, const float* d_film
   YK_GUARD_BEGIN
   HIPCHK(hipSetDevice(d->ordinal));
   const long long npx = (long long)p->width * p->height;
-  launch(k_film_resolve, grid_for(npx), 256, 0, d->stream, d_film, d_rgba, npx);
+  launch(k_film_resolve, grid_for(npx), 256, 0, d->stream, d_film, d_rgba, npx, p->premult_alpha ? 1 : 0);
   HIPCHK(hipStreamSynchronize(d->stream));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_depth_resolve(yk_device* d, const yk_render_params* p, const float* d_depth, float* d_z) {
+  if (!d || !p || !d_depth || !d_z) return set_error(YK_ERR_ARG, "yk_depth_resolve: NULL argument");
+  if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  const long long npx = (long long)p->width * p->height;
+  launch(k_depth_resolve, grid_for(npx), 256, 0, d->stream, d_depth, d_z, npx);
+  HIPCHK(hipStreamSynchronize(d->stream));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+// tiledIntegrator_t::precalcDepths (integrator.cc:99-130) and the maxDepth /
+// minDepth it starts from (integrator.cc:150-151).
+int yk_depth_range(yk_device* d, const yk_render_params* p, float* min_out, float* inv_range_out) {
+  if (!d || !p || !min_out || !inv_range_out) return set_error(YK_ERR_ARG, "yk_depth_range: NULL argument");
+  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_depth_range: no scene uploaded");
+  float min_depth = 1e38f, max_depth = 0.f;
+  YK_GUARD_BEGIN
+  if (d->cam_has_clip && d->cam_far_clip > -1) {
+    min_depth = d->cam_near_clip;
+    max_depth = d->cam_far_clip;
+  } else {
+    // a sample outside a circular angular camera's circle is traced with an
+    // uninitialised direction there: nothing to restate
+    if (cam_can_die(d))
+      return set_error(YK_ERR_UNSUPPORTED,
+                       "yk_depth_range: a circular angular camera without a far clip (the reference traces its "
+                       "samples outside the circle with an uninitialised direction)");
+    const long long n = (long long)d->cam_resx * d->cam_resy;
+    if (d->cam_resx <= 0 || d->cam_resy <= 0 || n > (1ll << 28))
+      return set_error(YK_ERR_ARG, "yk_depth_range: the camera's resolution is empty or too large");
+    HIPCHK(hipSetDevice(d->ordinal));
+    bind_constants(d);
+    DBuf<yk_ray> rays;
+    DBuf<yk_hit> hits;
+    DBuf<unsigned> mm;
+    rays.ensure((size_t)n);
+    hits.ensure((size_t)n);
+    mm.ensure(2);
+    float init[2] = {0.f, 1e38f};
+    HIPCHK(hipMemcpy(mm.p, init, sizeof init, hipMemcpyHostToDevice));
+    auto* shoot = d->cam_host.kind == YK_CAMERA_ORTHOGRAPHIC ? k_depth_range_rays<YK_CAMERA_ORTHOGRAPHIC>
+                  : d->cam_host.kind == YK_CAMERA_ANGULAR    ? k_depth_range_rays<YK_CAMERA_ANGULAR>
+                                                             : k_depth_range_rays<YK_CAMERA_PERSPECTIVE>;
+    launch(shoot, grid_for(n), 256, 0, d->stream, d->cam_resx, d->cam_resy, rays.p);
+    yk_stats local{};
+    launch_trace<true>(d, d->pipe[0], rays.p, n, hits.p, nullptr, &local);  // d->stream is pipe 0's
+    launch(k_depth_range_reduce, grid_for(n), 256, 0, d->stream, (const yk_ray*)rays.p, (const yk_hit*)hits.p, n, mm.p);
+    HIPCHK(hipStreamSynchronize(d->stream));
+    float out[2];
+    HIPCHK(hipMemcpy(out, mm.p, sizeof out, hipMemcpyDeviceToHost));
+    max_depth = out[0];
+    min_depth = out[1];
+  }
+  if (max_depth > 0.f) max_depth = 1.f / (max_depth - min_depth);
+  *min_out = min_depth;
+  *inv_range_out = max_depth;
   return YK_OK;
   YK_GUARD_END
 }
@@ -751,15 +852,23 @@ int yk_render_film(yk_device* d, const yk_render_params* p, int32_t shard, int32
                    yk_stats* st) {
   if (!d || !p || !film_host) return set_error(YK_ERR_ARG, "yk_render_film: NULL argument");
   if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
+  if (const int rc = check_depth_params(p)) return rc;
   YK_GUARD_BEGIN
   HIPCHK(hipSetDevice(d->ordinal));
   const size_t npx = (size_t)p->width * p->height;
-  DBuf<float> film;
+  DBuf<float> film, depth;
   film.ensure(npx * 5);
   HIPCHK(hipMemsetAsync(film.p, 0, npx * 5 * sizeof(float), d->stream));
-  const int rc = yk_render_shard(d, p, shard, nshards, film.p, st);
+  yk_render_params q = *p;
+  if (p->z_channel) {  // the depth film is host memory here: a device film of the call's own
+    depth.ensure(npx * 2);
+    HIPCHK(hipMemsetAsync(depth.p, 0, npx * 2 * sizeof(float), d->stream));
+    q.depth_film = depth.p;
+  }
+  const int rc = yk_render_shard(d, &q, shard, nshards, film.p, st);
   if (rc != YK_OK) return rc;
   HIPCHK(hipMemcpy(film_host, film.p, npx * 5 * sizeof(float), hipMemcpyDeviceToHost));
+  if (p->z_channel) HIPCHK(hipMemcpy(p->depth_film, depth.p, npx * 2 * sizeof(float), hipMemcpyDeviceToHost));
   return YK_OK;
   YK_GUARD_END
 }
@@ -793,14 +902,23 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
   }
   if (p->aa_passes < 1) return set_error(YK_ERR_ARG, "AA_passes must be >= 1");
   if (p->width <= 0 || p->height <= 0) return set_error(YK_ERR_ARG, "empty render area");
+  if (const int rc = check_depth_params(p)) return rc;
   YK_GUARD_BEGIN
   const size_t npx = (size_t)p->width * p->height, nfl = npx * 5;
+  // z_channel: every device keeps a shard depth film next to its shard film,
+  // reduced the same way (k_film_sum, shard order) into p->depth_film (host)
+  const bool zch = p->z_channel != 0;
+  const size_t ndf = npx * 2;
   yk_device* d0 = devs[0];
   // shard films and reduce buffers live on the handles: sized once, reused
   for (int i = 0; i < ndev; ++i) {
     HIPCHK(hipSetDevice(devs[i]->ordinal));
     devs[i]->mfilm.ensure(nfl);
     HIPCHK(hipMemsetAsync(devs[i]->mfilm.p, 0, nfl * sizeof(float), devs[i]->stream));
+    if (zch) {
+      devs[i]->mdepth.ensure(ndf);
+      HIPCHK(hipMemsetAsync(devs[i]->mdepth.p, 0, ndf * sizeof(float), devs[i]->stream));
+    }
     HIPCHK(hipStreamSynchronize(devs[i]->stream));
     if (devs[i]->ordinal != d0->ordinal) {  // direct xGMI access where the pair allows it
       int can = 0;
@@ -815,8 +933,9 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
   }
   HIPCHK(hipSetDevice(d0->ordinal));
   d0->macc.ensure(nfl);
-  FilmShards FS{};
-  FS.n = ndev;
+  if (zch) d0->mdacc.ensure(ndf);
+  FilmShards FS{}, FSD{};
+  FS.n = FSD.n = ndev;
   // YK_MULTI_STAGE_ALL=1 (test only): shards on d0's own GPU also take the
   // peer path (staging film, copy stream, event), so one-GPU boxes run it
   const bool stage_all = [] {
@@ -829,9 +948,14 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
     // into a staging film first, on a copy stream of its own
     if (!staged(i)) {
       FS.f[i] = devs[i]->mfilm.p;
+      FSD.f[i] = zch ? devs[i]->mdepth.p : nullptr;
       continue;
     }
     d0->mstage[i].ensure(nfl);
+    if (zch) {
+      d0->mdstage[i].ensure(ndf);
+      FSD.f[i] = d0->mdstage[i].p;
+    }
     if (!d0->mstream[i]) HIPCHK(hipStreamCreateWithFlags(&d0->mstream[i], hipStreamNonBlocking));
     if (!d0->mevent[i]) HIPCHK(hipEventCreateWithFlags(&d0->mevent[i], hipEventDisableTiming));
     FS.f[i] = d0->mstage[i].p;
@@ -845,7 +969,9 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
     std::vector<std::thread> th;
     for (int i = 0; i < ndev; ++i)
       th.emplace_back([&, i] {
-        rc[i] = render_pass(devs[i], p, i, ndev, devs[i]->mfilm.p, &sts[i], ps);
+        PassSpec psi = ps;
+        psi.d_depth = zch ? devs[i]->mdepth.p : nullptr;
+        rc[i] = render_pass(devs[i], p, i, ndev, devs[i]->mfilm.p, &sts[i], psi);
         if (rc[i] != YK_OK) msg[i] = yk_last_error();
       });
     for (auto& t : th) t.join();
@@ -867,10 +993,14 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
       if (!staged(i)) continue;
       HIPCHK(hipMemcpyPeerAsync(d0->mstage[i].p, d0->ordinal, devs[i]->mfilm.p, devs[i]->ordinal, nfl * sizeof(float),
                                 d0->mstream[i]));
+      if (zch)
+        HIPCHK(hipMemcpyPeerAsync(d0->mdstage[i].p, d0->ordinal, devs[i]->mdepth.p, devs[i]->ordinal,
+                                  ndf * sizeof(float), d0->mstream[i]));
       HIPCHK(hipEventRecord(d0->mevent[i], d0->mstream[i]));
       HIPCHK(hipStreamWaitEvent(s0, d0->mevent[i], 0));
     }
     launch(k_film_sum, grid_for(((long long)nfl + 3) / 4), 256, 0, s0, d0->macc.p, FS, (long long)nfl);
+    if (zch) launch(k_film_sum, grid_for(((long long)ndf + 3) / 4), 256, 0, s0, d0->mdacc.p, FSD, (long long)ndf);
     HIPCHK(hipStreamSynchronize(s0));
     ms_reduce += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   };
@@ -892,6 +1022,7 @@ int yk_render_multi(yk_device* const* devs, int32_t ndev, const yk_render_params
   }
   HIPCHK(hipSetDevice(d0->ordinal));
   HIPCHK(hipMemcpy(film_host, d0->macc.p, nfl * sizeof(float), hipMemcpyDeviceToHost));
+  if (zch) HIPCHK(hipMemcpy(p->depth_film, d0->mdacc.p, ndf * sizeof(float), hipMemcpyDeviceToHost));
   if (st) {
     for (const yk_stats& x : sts) {
       add_trace_stats(st, true, x.closest_rays, x.closest_nodes, x.closest_tris, x.ms_closest, x.closest_launches);
@@ -916,8 +1047,10 @@ int yk_render(yk_device* d, const yk_render_params* p, float* rgba_host, yk_stat
   film.ensure(npx * 5);
   rgba.ensure(npx * 4);
   HIPCHK(hipMemsetAsync(film.p, 0, npx * 5 * sizeof(float), d->stream));
-  int rc = yk_render_shard(d, p, 0, 1, film.p, st);
-  if (rc == YK_OK) rc = yk_film_resolve(d, p, film.p, rgba.p);
+  yk_render_params q = *p;  // RGBA only: no depth film is produced here
+  q.z_channel = 0;
+  int rc = yk_render_shard(d, &q, 0, 1, film.p, st);
+  if (rc == YK_OK) rc = yk_film_resolve(d, &q, film.p, rgba.p);
   if (rc == YK_OK) HIPCHK(hipMemcpy(rgba_host, rgba.p, npx * 4 * sizeof(float), hipMemcpyDeviceToHost));
   return rc;
   YK_GUARD_END

@@ -264,14 +264,13 @@ extern "C" int yk_debug_last_plan(yk_device* d, yk_last_plan* out) {
   return YK_OK;
 }
 
-// yk_debug_film_splat: host samples through the renderer's tile lists
-// (owned_tiles, build_tile_lists) and its gather launch (launch_film_gather),
-// in buffers of the call's own.
-extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, int32_t spp,
-                                   int32_t tiles_per_batch, const uint8_t* flags, const float* colours,
-                                   const float* offsets, int64_t n, float* film) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_film_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+// yk_debug_film_splat / yk_debug_depth_splat: host samples through the
+// renderer's tile lists (owned_tiles, build_tile_lists) and its gather launch
+// (launch_film_gather), in buffers of the call's own. depth: `colours` holds
+// one float per sample and the film is {val, weight}.
+static int debug_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, int32_t spp,
+                       int32_t tiles_per_batch, const uint8_t* flags, const float* colours, const float* offsets,
+                       int64_t n, float* film, bool depth) {
   if (!d || !p || !film || n < 0 || n > (1ll << 24) || (n > 0 && (!colours || !offsets)) || nshards < 1 || shard < 0 ||
       shard >= nshards || spp < 1)
     return set_error(YK_ERR_ARG, "yk_debug_film_splat: bad arguments");
@@ -306,14 +305,15 @@ extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int3
   }
   if (total != n) return set_error(YK_ERR_ARG, "yk_debug_film_splat: n is not the sample count of the tile lists");
   HIPCHK(hipSetDevice(d->ordinal));
-  const size_t nfl = (size_t)F.w * F.h * 5;
+  const size_t nfl = (size_t)F.w * F.h * (depth ? 2 : 5);
+  const size_t per = depth ? 1 : 4;  // floats per sample
   DBuf<float> dfilm;
-  DBuf<float4> dcol;
+  DBuf<float> dcol;
   DBuf<float2> dxy;
   DBuf<char4> dext;
   DBuf<int> dbase, dpmap, drank;
   dfilm.ensure(nfl);
-  dcol.ensure((size_t)maxnc);
+  dcol.ensure((size_t)maxnc * per);
   dxy.ensure((size_t)maxnc);
   dext.ensure((size_t)maxnc);  // one per pixel slot; maxnc bounds the slots of any spp
   dbase.ensure(std::max<size_t>(1, L.base.size()));
@@ -335,17 +335,35 @@ extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int3
     if (nc > 0) {
       // the batch's buffers are reused: the copies wait for the previous gather
       HIPCHK(hipStreamSynchronize(d->stream));
-      HIPCHK(hipMemcpy(dcol.p, colours + 4 * at, (size_t)nc * sizeof(float4), hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(dcol.p, colours + per * at, (size_t)nc * per * sizeof(float), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(dxy.p, offsets + 2 * at, (size_t)nc * sizeof(float2), hipMemcpyHostToDevice));
     }
-    launch_film_gather(d->stream, F, flags ? dpmap.p : nullptr, tb0, tb1, L.rect_of[bi], nc, dcol.p, dxy.p,
-                       dbase.p + (size_t)bi * (tpb + 1), dext.p, dfilm.p);
+    launch_film_gather(d->stream, F, flags ? dpmap.p : nullptr, tb0, tb1, L.rect_of[bi], nc,
+                       depth ? nullptr : reinterpret_cast<const float4*>(dcol.p), dxy.p,
+                       dbase.p + (size_t)bi * (tpb + 1), dext.p, dfilm.p, film_options(p), depth ? dcol.p : nullptr,
+                       depth ? dfilm.p : nullptr);
     at += nc;
   }
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipMemcpy(film, dfilm.p, nfl * sizeof(float), hipMemcpyDeviceToHost));
   return YK_OK;
   YK_GUARD_END
+}
+
+extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, int32_t spp,
+                                   int32_t tiles_per_batch, const uint8_t* flags, const float* colours,
+                                   const float* offsets, int64_t n, float* film) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_film_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+  return debug_splat(d, p, shard, nshards, spp, tiles_per_batch, flags, colours, offsets, n, film, false);
+}
+
+extern "C" int yk_debug_depth_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards,
+                                    int32_t spp, int32_t tiles_per_batch, const uint8_t* flags, const float* depths,
+                                    const float* offsets, int64_t n, float* film) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_depth_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+  return debug_splat(d, p, shard, nshards, spp, tiles_per_batch, flags, depths, offsets, n, film, true);
 }
 
 // yk_debug_aa_flags: next_pass_flags, the adaptive passes' own path, on an

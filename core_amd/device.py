@@ -88,11 +88,35 @@ class Device:
     def new_film(self, params):
         return torch.zeros((params.height, params.width, 5), dtype=torch.float32, device=self.torch_device)
 
-    def render_shard(self, params, film, shard=0, nshards=1, stats=None):
+    def new_depth_film(self, params):
+        """(h, w, 2) zeros: the {val, weight} sums of the depth channel (params.z_channel)"""
+        return torch.zeros((params.height, params.width, 2), dtype=torch.float32, device=self.torch_device)
+
+    def render_shard(self, params, film, shard=0, nshards=1, stats=None, depth_film=None):
+        """depth_film: a new_depth_film() tensor; the call renders with z_channel
+        set and adds the depth sums to it (params itself is left as it is)"""
         torch.cuda.synchronize(self.torch_device)
         st = stats if stats is not None else A.yk_stats()
+        if depth_film is not None:
+            params = params.copy()
+            params.z_channel = 1
+            params.depth_film = depth_film.data_ptr()
         A.check(A.lib().yk_render_shard(self._p, C.byref(params), shard, nshards, _ptr(film), C.byref(st)))
         return st
+
+    def depth_range(self, params):
+        """tiledIntegrator_t::precalcDepths for the resident scene and camera
+        (yk_depth_range) -> (depth_min, depth_inv_range) as float32"""
+        lo, inv = C.c_float(), C.c_float()
+        A.check(A.lib().yk_depth_range(self._p, C.byref(params), C.byref(lo), C.byref(inv)))
+        return np.float32(lo.value), np.float32(inv.value)
+
+    def depth_resolve(self, params, depth_film):
+        """pixelGray_t::normalized of a depth film -> (h, w) float32 tensor"""
+        z = torch.empty((params.height, params.width), dtype=torch.float32, device=self.torch_device)
+        torch.cuda.synchronize(self.torch_device)
+        A.check(A.lib().yk_depth_resolve(self._p, C.byref(params), _ptr(depth_film), _ptr(z)))
+        return z
 
     def set_abort(self, fn):
         """yk_device_set_abort: fn() -> bool is polled between batches; None removes it."""
@@ -111,7 +135,13 @@ class Device:
         arr = (C.c_void_p * len(devices))(*[d._p.value for d in devices])
         out = np.zeros((params.height, params.width, 5), np.float32)
         st = stats if stats is not None else A.yk_stats()
+        depth = None
+        if params.z_channel:  # the reduced depth sums come back as st.depth_film, (h, w, 2)
+            params = params.copy()
+            depth = np.zeros((params.height, params.width, 2), np.float32)
+            params.depth_film = depth.ctypes.data
         rc = A.lib().yk_render_multi(arr, len(devices), C.byref(params), out.ctypes.data_as(A.fp), C.byref(st))
+        st.depth_film = depth
         st.aborted = rc == A.YK_ERR_ABORTED
         if not st.aborted:
             A.check(rc)

@@ -219,6 +219,35 @@ typedef struct yk_render_params {
    * photon.caustic_photons ("photons"), caustic_mix, caustic_radius and
    * bounces ("caustic_depth"), as path tracing's photon caustics do. */
   int32_t dl_caustics;
+  /* Film options (appended: the offsets above are what earlier callers compiled
+   * against, and a zero-initialised tail renders exactly as before).
+   * z_channel ("z_channel", scene_t::doDepth()): every camera sample that
+   * carries a ray also splats one depth value into depth_film
+   * (imageFilm_t::addDepthSample, imagefilm.cc:513-564; integrator.cc:313-334).
+   * Raw: the camera hit's t, the camera ray's far-plane tmax on a miss, and
+   * 99999997952.f where that is <= 0. normalize_z_channel
+   * ("normalize_z_channel"): 1 - (tmax - depth_min) * depth_inv_range where
+   * tmax > 0, else 0; depth_min / depth_inv_range are the reference's minDepth
+   * and maxDepth after tiledIntegrator_t::precalcDepths (yk_depth_range).
+   * depth_film: width*height*{val, weight} floats, caller-zeroed, in the
+   * memory space of the call's film argument (device for yk_render_shard, host
+   * for yk_render_film and yk_render_multi). YK_ERR_ARG: z_channel without a
+   * depth_film; normalize_z_channel with a non-finite depth_min
+   * (depth_inv_range may be inf, as in the reference). */
+  int32_t z_channel;
+  int32_t normalize_z_channel;
+  float depth_min;
+  float depth_inv_range;
+  float* depth_film;
+  /* "premult" (imageFilm_t::premultAlpha): addSample premultiplies its local
+   * copy of the sample inside the pixel loop (imagefilm.cc:502), so the m-th
+   * pixel of the sample's window (row-major, after the clamp to the film area)
+   * takes the colour premultiplied m times; yk_film_resolve premultiplies once
+   * more after its clamp, as flush does (imagefilm.cc:423).
+   * "clamp_rgb" (imageFilm_t::clamp): clampRGB01 once per sample, before the
+   * splat and before any premultiply (imagefilm.cc:457). */
+  int32_t premult_alpha;
+  int32_t clamp_rgb;
 } yk_render_params;
 enum { YK_TILES_LINEAR = 0, YK_TILES_RANDOM = 1 };
 
@@ -501,11 +530,32 @@ int yk_trace_shadow_filtered(yk_device* d, const yk_ray* d_rays, int64_t n, uint
 
 /* Render the tiles t with (t % nshards == shard) and accumulate the film
  * sums (R,G,B,A,weight per pixel, width*height*5 floats, pixel-major) into
- * d_film (device pointer, caller-allocated, caller-zeroed). */
+ * d_film (device pointer, caller-allocated, caller-zeroed). With
+ * p->z_channel the depth sums go to p->depth_film (device) likewise. */
 int yk_render_shard(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards,
                     float* d_film, yk_stats* st);
-/* imageFilm_t::flush normalisation (+clampRGB0): film sums -> RGBA floats */
+/* imageFilm_t::flush normalisation (+clampRGB0): film sums -> RGBA floats;
+ * with p->premult_alpha the clamped pixel is premultiplied (RGB *= A) */
 int yk_film_resolve(yk_device* d, const yk_render_params* p, const float* d_film, float* d_rgba);
+/* tiledIntegrator_t::precalcDepths (integrator.cc:99-130) for the resident
+ * scene and camera: *min_out / *inv_range_out are minDepth and maxDepth as
+ * render() holds them afterwards (p->depth_min / p->depth_inv_range). A camera
+ * set from parameters with far_clip > -1 gives its near and far clip; otherwise
+ * one ray per pixel of the camera's resolution is shot at (row, column, 0.5,
+ * 0.5) -- the reference passes the row index as px -- and traced, tmax of a
+ * hit being its t: max over tmax from 0, min over tmax >= 0 from 1e38f. Then
+ * maxDepth > 0 becomes 1 / (maxDepth - minDepth). A camera set as object state
+ * (yk_scene_set_camera_state) carries no clip values: the rays are shot, and
+ * the caller that holds the live camera takes its getNearClip / getFarClip
+ * itself when far_clip > -1. YK_ERR_UNSUPPORTED for a circular angular camera
+ * on the ray branch: the reference traces its samples outside the circle with
+ * an uninitialised direction (angularCamera.cc:52-59, vector3d.h:56). p gives
+ * nothing but its presence today (reserved for options); it must not be NULL. */
+int yk_depth_range(yk_device* d, const yk_render_params* p, float* min_out, float* inv_range_out);
+/* pixelGray_t::normalized (image_buffers.h:50-54): depth sums (width*height*
+ * {val, weight}, device) -> width*height floats (device): weight > 0 ?
+ * val / weight : 0, a float division */
+int yk_depth_resolve(yk_device* d, const yk_render_params* p, const float* d_depth, float* d_z);
 /* convenience for host callers (the reference plugin): render the tiles of
  * `shard` and return the film sums (width*height*5 floats) in host memory */
 int yk_render_film(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, float* film_host,
@@ -590,8 +640,9 @@ int yk_device_build_tree(yk_device* d, const yk_scene* s, int32_t flags, yk_tree
 int yk_device_export_tree(yk_device* d, uint32_t* nodes, int64_t node_cap, uint32_t* leaf, int64_t leaf_cap,
                           int64_t* nnodes_out, int64_t* nleaf_out);
 /* Test-only hooks (the watchdog's tree damage, the lights' function probe)
- * are declared in yk_test_hooks.h, yk_test_hooks_light.h and
- * yk_test_hooks_camera.h, not here, and are disabled unless YK_DEBUG_HOOKS=1. */
+ * are declared in yk_test_hooks.h, yk_test_hooks_light.h,
+ * yk_test_hooks_camera.h, yk_test_hooks_film.h and yk_test_hooks_depth.h, not
+ * here, and are disabled unless YK_DEBUG_HOOKS=1. */
 
 #ifdef __cplusplus
 }

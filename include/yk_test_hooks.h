@@ -75,7 +75,7 @@ typedef struct yk_batch_plan_in {
   int32_t tile;           /* tile edge in pixels */
   int32_t spp;            /* camera samples per pixel of the pass */
   int32_t pipes;          /* YK_PIPES, 1..4 */
-  int32_t reserved;
+  int32_t reserved;       /* bit 0: z_channel, 4 B per sample more (the depth samples); other bits 0 */
   int64_t owned_tiles;    /* tiles of this shard */
   int64_t target_samples; /* YK_BATCH_SAMPLES; <= 0: unset (32M) */
   int64_t budget_bytes;   /* HBM for the batch buffers of all pipes (YK_BATCH_GB) */

@@ -14,7 +14,8 @@ extern "C" {
  * tile lists and its extent + gather launches (one stream, batch after batch).
  *
  * Read from p: the render area (xstart, ystart, width, height), tile_size,
- * filter, aa_pixelwidth / filter_width and tile_order. The pass is that of
+ * filter, aa_pixelwidth / filter_width, tile_order, and premult_alpha /
+ * clamp_rgb (the gather's compile-time variants). The pass is that of
  * shard `shard` of `nshards` with spp samples per pixel in batches of
  * tiles_per_batch owned tiles (<= 0: all of them in one batch). flags is NULL,
  * or width*height bytes (film-local, row-major) of an adaptive pass: only

@@ -19,8 +19,9 @@
 //                 k_film_resolve does
 // What the GPU path cannot reproduce is refused with an error, never rendered
 // differently: textured (shader-node) materials, other lights / backgrounds /
-// cameras / volume integrators, film filters libyk does not build, premultiplied
-// alpha (compounded per pixel, imagefilm.cc:502), depth passes.
+// cameras / volume integrators, film filters libyk does not build.
+// Premultiplied alpha (compounded per pixel, imagefilm.cc:502), clamp_rgb and
+// the depth channel are film options of the GPU path (yk_render_params).
 #include <core_api/environment.h>
 #include <core_api/imagefilm.h>
 #include <core_api/scene.h>
@@ -150,6 +151,8 @@ YK_MEMBER(FilmFilterW, imageFilm_t, float, filterw)
 YK_MEMBER(FilmTable, imageFilm_t, float*, filterTable)
 YK_MEMBER(FilmTileSize, imageFilm_t, int, tileSize)
 YK_MEMBER(FilmPremult, imageFilm_t, bool, premultAlpha)
+YK_MEMBER(FilmClamp, imageFilm_t, bool, clamp)
+YK_MEMBER(FilmDepthMap, imageFilm_t, gray2DImage_t*, depthMap)
 YK_MEMBER(FilmSplitter, imageFilm_t, imageSpliter_t*, splitter)
 #define GET(obj, Tag) ((obj).*member_of<Tag>::ptr)
 
@@ -529,8 +532,30 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
     // 119-165) and takes filterw as the film holds it; a table it does not
     // build is refused
     if (yk_film_filter_from_table(GET(*film, FilmTable), GET(*film, FilmFilterW), &params) != YK_OK) return fail();
-    if (GET(*film, FilmPremult)) return unsupported("premultiplied alpha films are not on the GPU path");
-    if (scene->doDepth()) return unsupported("depth passes are not on the GPU path");
+    // film options: the gather's premultiply / clamp variants and the depth
+    // channel. Unverified member reads (clamp, depthMap), like the layout
+    // structs above: this plugin is not compiled in this repository's setup.
+    params.premult_alpha = GET(*film, FilmPremult) ? 1 : 0;
+    params.clamp_rgb = GET(*film, FilmClamp) ? 1 : 0;
+    gray2DImage_t* depth_map = GET(*film, FilmDepthMap);
+    params.z_channel = (scene->doDepth() && depth_map) ? 1 : 0;
+    params.normalize_z_channel = (params.z_channel && scene->normalizedDepth()) ? 1 : 0;
+    params.depth_min = 0.f;
+    params.depth_inv_range = 0.f;
+    if (params.normalize_z_channel) {
+      // tiledIntegrator_t::precalcDepths (integrator.cc:99-130). The scene was
+      // uploaded as object state, which carries no clip values: the far_clip
+      // > -1 branch reads the live camera, the ray branch runs on the device
+      const camera_t* cam = scene->getCamera();
+      if (cam->getFarClip() > -1) {
+        float lo = cam->getNearClip(), hi = cam->getFarClip();
+        if (hi > 0.f) hi = 1.f / (hi - lo);
+        params.depth_min = lo;
+        params.depth_inv_range = hi;
+      } else if (yk_depth_range(devs[0], &params, &params.depth_min, &params.depth_inv_range) != YK_OK) {
+        return fail();
+      }
+    }
     // as tiledIntegrator_t::render does (integrator.cc:148): clear the film and
     // build its tile splitter, whose order ("tiles_order": row-major, or
     // std::random_shuffle for "random", imagesplitter.cc:29-53) is the order
@@ -546,9 +571,12 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
     params.tile_order = order.empty() ? nullptr : order.data();
     params.tile_order_len = (int32_t)order.size();
     std::vector<float> sums((size_t)w * h * 5);
+    std::vector<float> dsums(params.z_channel ? (size_t)w * h * 2 : 0);
+    params.depth_film = params.z_channel ? dsums.data() : nullptr;  // host memory: yk_render_multi
     const int rc = yk_render_multi(devs.data(), (int32_t)devs.size(), &params, sums.data(), nullptr);
     params.tile_order = nullptr;  // `order` ends with this call
     params.tile_order_len = 0;
+    params.depth_film = nullptr;  // as does `dsums`
     if (rc != YK_OK && rc != YK_ERR_ABORTED) return fail();  // aborted: keep what was rendered, as renderTile does
     for (int j = 0; j < h; ++j)
       for (int i = 0; i < w; ++i) {
@@ -557,6 +585,15 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
         px.col = colorA_t(s[0], s[1], s[2], s[3]);
         px.weight = s[4];
       }
+    // the depth sums as addDepthSample leaves them; the film's flush does the
+    // division (pixelGray_t::normalized) and the final premultiply itself
+    if (params.z_channel)
+      for (int j = 0; j < h; ++j)
+        for (int i = 0; i < w; ++i) {
+          pixelGray_t& px = (*depth_map)(i, j);
+          px.val = dsums[2 * ((size_t)j * w + i)];
+          px.weight = dsums[2 * ((size_t)j * w + i) + 1];
+        }
     return true;
   }
 
