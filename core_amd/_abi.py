@@ -16,6 +16,8 @@ YK_ERR_ABORTED = 7
 YK_ERR_ARG, YK_ERR_STATE, YK_ERR_HIP, YK_ERR_UNSUPPORTED, YK_ERR_ALLOC, YK_ERR_INTERNAL = 1, 2, 3, 4, 5, 6
 YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT = 0, 1
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
+YK_LIGHT_MESH = 5
+YK_MESH_LIGHT_MAX_TRIS, YK_MESH_LIGHT_MAX_DEPTH = 65536, 29
 YK_MESH_SMOOTH, YK_MESH_NORMALS_EXPORTED = 1, 2
 YK_INTEGRATOR_DIRECT, YK_INTEGRATOR_PATH, YK_INTEGRATOR_PHOTON = 0, 1, 2
 YK_PHOTON_MAP_DIFFUSE, YK_PHOTON_MAP_CAUSTIC, YK_PHOTON_MAP_RADIANCE = 0, 1, 2
@@ -88,6 +90,16 @@ class yk_spot_light_state(C.Structure):
 class yk_sphere_light_state(C.Structure):
     _fields_ = [("center", f3), ("radius", C.c_float), ("square_radius", C.c_float),
                 ("square_radius_epsilon", C.c_float), ("area", C.c_float), ("color", f3), ("samples", C.c_int32)]
+
+
+class yk_mesh_light(C.Structure):
+    _fields_ = [("color", f3), ("power", C.c_float), ("samples", C.c_int32), ("double_sided", C.c_int32)]
+
+
+class yk_mesh_light_state(C.Structure):
+    _fields_ = [("color", f3), ("samples", C.c_int32), ("double_sided", C.c_int32), ("area", C.c_float),
+                ("inv_area", C.c_float), ("ntris", C.c_int32), ("tree_depth", C.c_int32),
+                ("tree_nodes", C.c_int32)]
 
 
 class yk_camera_state(C.Structure):
@@ -235,6 +247,10 @@ SIGNATURES = {
     "yk_scene_get_spot_light_state": (C.c_int, [P, i32, C.POINTER(yk_spot_light_state)]),
     "yk_scene_add_sphere_light_state": (C.c_int, [P, C.POINTER(yk_sphere_light_state)]),
     "yk_scene_get_sphere_light_state": (C.c_int, [P, i32, C.POINTER(yk_sphere_light_state)]),
+    "yk_scene_add_mesh_light": (C.c_int, [P, C.POINTER(yk_mesh_light), i32p, i32]),
+    "yk_scene_get_mesh_light": (C.c_int, [P, i32, C.POINTER(yk_mesh_light), i32p, i32, i32p]),
+    "yk_scene_get_mesh_light_state": (C.c_int, [P, i32, C.POINTER(yk_mesh_light_state), fp, fp, i32]),
+    "yk_scene_set_mesh_light_color": (C.c_int, [P, i32, fp]),
     "yk_scene_set_background": (C.c_int, [P, fp, C.c_float]),
     "yk_scene_get_background": (C.c_int, [P, fp, i32p]),
     "yk_scene_get_camera_state": (C.c_int, [P, C.POINTER(yk_camera_state)]),

@@ -198,6 +198,7 @@ int light_slots(const Scene& s, size_t i) {
     case YK_LIGHT_AREA: return 2 * s.light_states[i].samples;  // light samples + BSDF (MIS) samples
     case YK_LIGHT_SPOT: return s.spot_states[i].soft_shadows ? 2 * s.spot_states[i].samples : 1;
     case YK_LIGHT_SPHERE: return s.sphere_states[i].samples;  // canIntersect() is false: no MIS half
+    case YK_LIGHT_MESH: return 2 * s.mesh_lights[i].params.samples;  // canIntersect(): light + BSDF halves
     default: return 1;
   }
 }
@@ -303,6 +304,7 @@ void Scene::add_light(const yk_light& l) {
                                                                                   : yk_dirac_light_state{});
   spot_states.push_back(l.type == YK_LIGHT_SPOT ? spot_state(l) : yk_spot_light_state{});
   sphere_states.push_back(l.type == YK_LIGHT_SPHERE ? sphere_state(l) : yk_sphere_light_state{});
+  mesh_lights.emplace_back();
 }
 void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   lights.push_back(yk_light{});
@@ -314,6 +316,7 @@ void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   dirac_states.push_back(l);
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.emplace_back();
 }
 void Scene::add_light_state(const yk_area_light_state& l) {
   lights.push_back(yk_light{});
@@ -323,6 +326,7 @@ void Scene::add_light_state(const yk_area_light_state& l) {
   dirac_states.push_back(yk_dirac_light_state{});
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.emplace_back();
 }
 void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   lights.push_back(yk_light{});
@@ -334,6 +338,7 @@ void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   dirac_states.push_back(yk_dirac_light_state{});
   spot_states.push_back(l);
   sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.emplace_back();
 }
 void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   lights.push_back(yk_light{});
@@ -345,6 +350,32 @@ void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   dirac_states.push_back(yk_dirac_light_state{});
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(l);
+  mesh_lights.emplace_back();
+}
+// meshLight_t::factory (meshlight.cc:221-236): color * (CFLOAT)power * M_PI,
+// both through color_t's operator*(color_t, CFLOAT): float products
+void Scene::add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int nobj) {
+  MeshLight m;
+  m.params = l;
+  m.params.double_sided = l.double_sided ? 1 : 0;
+  for (int k = 0; k < 3; ++k) m.color[k] = (l.color[k] * l.power) * (float)3.14159265358979323846;
+  m.obj_ids.assign(obj_ids, obj_ids + nobj);
+  yk_light p{};
+  p.type = YK_LIGHT_MESH;
+  for (int k = 0; k < 3; ++k) p.color[k] = l.color[k];
+  p.power = l.power;
+  p.samples = l.samples;
+  lights.push_back(p);
+  light_has_params.push_back(true);
+  light_kind.push_back(YK_LIGHT_MESH);
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(a);
+  dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.push_back(std::move(m));
+  built = false;
 }
 void Scene::set_camera(const yk_camera& c) {
   camera = c;
@@ -418,6 +449,55 @@ static void normalize3(float* v) {
   }
 }
 
+// meshLight_t::initIS (meshlight.cc:47-65), source order: the triangles of
+// the light's meshes in getPrimitives order, triangle_t::surfaceArea
+// (triangle.cc:144-154: float cross product and length, the 0.5 * in double),
+// the double running total, pdf1D_t's cdf (CumulateStep1dDF, sample_utils.h:
+// 85-98) and the light's own triKdTree_t(tris, nTris, -1, 1, 0.8, 0.33)
+static void init_mesh_light(const Scene& S, MeshLight& L) {
+  L.verts.clear();
+  L.normals.clear();
+  L.areas.clear();
+  for (const int32_t id : L.obj_ids) {
+    const Mesh& m = S.meshes[(size_t)id - 1];
+    const size_t nf = m.faces.size() / 3;
+    const int np = (int)(m.points.size() / 3);
+    for (size_t f = 0; f < nf; ++f) {
+      float tv[9];
+      for (int k = 0; k < 3; ++k) {
+        const int vi = m.faces[3 * f + k];
+        if (vi < 0 || vi >= np) throw std::invalid_argument("mesh face references a missing vertex");
+        for (int c = 0; c < 3; ++c) tv[3 * k + c] = m.points[3 * vi + c];
+      }
+      L.verts.insert(L.verts.end(), tv, tv + 9);
+      float nrm[3];
+      rec_normal(tv, nrm);
+      L.normals.insert(L.normals.end(), nrm, nrm + 3);
+      const float e1x = tv[3] - tv[0], e1y = tv[4] - tv[1], e1z = tv[5] - tv[2];
+      const float e2x = tv[6] - tv[0], e2y = tv[7] - tv[1], e2z = tv[8] - tv[2];
+      const float x = e1y * e2z - e1z * e2y, y = e1z * e2x - e1x * e2z, z = e1x * e2y - e1y * e2x;
+      L.areas.push_back((float)(0.5 * (double)std::sqrt(x * x + y * y + z * z)));
+    }
+  }
+  const int n = (int)L.areas.size();
+  if (n == 0) throw std::invalid_argument("mesh light has no triangles");
+  double total = 0.0;
+  for (int i = 0; i < n; ++i) total += (double)L.areas[i];
+  L.area = (float)total;
+  L.inv_area = (float)(1.0 / total);
+  L.cdf.assign((size_t)n + 1, 0.f);
+  double c = 0.0;
+  const double delta = 1.0 / (double)n;
+  for (int i = 1; i < n + 1; ++i) {
+    c += (double)L.areas[i - 1] * delta;
+    L.cdf[i] = (float)c;
+  }
+  const float integral = (float)c;
+  if (!(total > 0.0) || !(integral > 0.f)) throw std::invalid_argument("mesh light has zero total area");
+  for (int i = 1; i < n + 1; ++i) L.cdf[i] /= integral;
+  build_kdtree(L.verts.data(), n, L.tree, -1, 1, 0.8f, 0.33f);
+}
+
 void Scene::finalize() {
   // scene_t::update, scene.cc:755-782: visible non-base TRIM meshes and
   // instances in object id order, triangles in insertion order. Universal
@@ -488,6 +568,8 @@ void Scene::finalize() {
   const int ntris = (int)tri_material.size();
   if (ntris == 0) throw std::invalid_argument("scene is empty");
   build_kdtree(tri_verts.data(), ntris, tree);
+  for (MeshLight& L : mesh_lights)
+    if (!L.obj_ids.empty()) init_mesh_light(*this, L);
   static std::atomic<uint64_t> next_generation{1};
   generation = next_generation.fetch_add(1);
   built = true;

@@ -34,6 +34,20 @@ struct Mesh {
   float m[16] = {};
 };
 
+// meshLight_t: parameters, the yk meshes whose triangles it holds, and after
+// finalize() the members initIS computes (meshlight.cc:47-65)
+struct MeshLight {
+  yk_mesh_light params{};
+  float color[3] = {0.f, 0.f, 0.f};  // color * (float)power * M_PI
+  std::vector<int32_t> obj_ids;      // 1-based, light order
+  std::vector<float> verts;          // 9 floats per triangle, getPrimitives order
+  std::vector<float> normals;        // triangle_t::normal, 3 per triangle
+  std::vector<float> areas;          // triangle_t::surfaceArea
+  std::vector<float> cdf;            // pdf1D_t::cdf, n + 1
+  float area = 0.f, inv_area = 0.f;
+  KdTree tree;
+};
+
 struct Scene {
   std::vector<Mesh> meshes;          // object-id order
   int mode = YK_MODE_TRIANGLE;       // scene_t::mode: which meshes the tree holds
@@ -51,6 +65,7 @@ struct Scene {
   std::vector<yk_dirac_light_state> dirac_states;   // point / directional (zero entry for area lights)
   std::vector<yk_spot_light_state> spot_states;     // spot lights (zero entry for every other kind)
   std::vector<yk_sphere_light_state> sphere_states; // sphere lights (zero entry for every other kind)
+  std::vector<MeshLight> mesh_lights;               // mesh lights (empty entry for every other kind)
   bool has_background = false;
   float background[3] = {0.f, 0.f, 0.f};            // constBackground_t::color (color*power)
   yk_camera_state camera_state{};
@@ -63,6 +78,7 @@ struct Scene {
   void add_dirac_light_state(const yk_dirac_light_state& l);
   void add_spot_light_state(const yk_spot_light_state& l);
   void add_sphere_light_state(const yk_sphere_light_state& l);
+  void add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int nobj);
   void set_camera(const yk_camera& c);
   void set_camera_state(const yk_camera_state& c);
 

@@ -91,6 +91,28 @@ struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-4
   int photon_only;  // illuminate / illumSample return false
   // sphereLight_t members (spherelight.cc:56-61): pos = center, radius, area, and
   float sq_radius, sq_radius_eps;
+  // meshLight_t members (meshlight.h:56-64): area (above), doubleSided, and
+  // the light's record in DScene::ml (cdf, triangles, normals, its own tree)
+  int double_sided;
+  int mesh;
+};
+
+// One mesh light's arrays, resident per device handle (yk_device_upload) and
+// reached through DScene::ml[DLight::mesh]: pdf1D_t's cdf, the triangles in
+// light order (triangleObject_t::getPrimitives) as vertices for
+// triangle_t::sample and as a / e1 / e2 records for the hit test, their
+// triangle_t::normal, and the light's triKdTree_t in the scene tree's node
+// encoding with one padding node.
+struct DMeshLight {
+  const float* cdf;      // n + 1
+  const float* verts;    // 9 per triangle: a, b, c
+  const float* tris;     // kTriWords per triangle: a, e1, e2
+  const float* nrm;      // 3 per triangle
+  const uint2* nodes;
+  const uint32_t* leaf;
+  float bound[6];
+  int n;
+  unsigned nnodes, depth_cap, nleaf;
 };
 
 struct DCam {  // the camera after camera_t ctor + setAxis (yk_camera_state)
@@ -132,6 +154,7 @@ struct DScene {
   unsigned ntris;      // records in tris
   unsigned nlref;      // leaf-list entries (records in ltris)
   int uni;             // universal mode (vTriangle_t getSurface: b0 = 0; IntersectS t > tmin)
+  const DMeshLight* ml;  // mesh-light records (null without a mesh light)
 };
 
 __device__ __forceinline__ v3 ld3(const float* p) { return V3(p[0], p[1], p[2]); }
@@ -444,8 +467,8 @@ __device__ __forceinline__ bool leaf_test(const DScene& S, Trav& st, uint32_t p,
 
 // Per-lane step (the transparent-shadow kernel, whose leaf body is
 // sequential: IntersectTS filters each transparent prim once, in leaf order).
-template <bool CLOSEST, bool TS = false>
-__device__ __forceinline__ bool trav_step(const DScene& S, Trav& st, const LaneStack& stk, unsigned& nnodes,
+template <bool CLOSEST, bool TS = false, class STK = LaneStack>
+__device__ __forceinline__ bool trav_step(const DScene& S, Trav& st, const STK& stk, unsigned& nnodes,
                                           unsigned& ntris, bool& occluded) {
   if (st.dist < st.en_t) return true;
   int node = st.node;
@@ -2096,6 +2119,129 @@ __device__ __forceinline__ bool sphere_hit(const DLight& L, v3 from, v3 dir, flo
   return true;
 }
 
+// pdf1D_t::DSample (sample_utils.h:141-157): u == 0 answers 0; otherwise
+// std::lower_bound over cdf[0..n] (the first entry >= u), minus 1, clamped at 0
+__device__ __forceinline__ int mesh_dsample(const float* cdf, int n, float u) {
+  if (u == 0.f) return 0;
+  int lo = 0, len = n + 1;
+  while (len > 0) {  // std::lower_bound
+    const int half = len >> 1;
+    if (cdf[lo + half] < u) {
+      lo += half + 1;
+      len -= half + 1;
+    } else {
+      len = half;
+    }
+  }
+  const int index = lo - 1;
+  return index < 0 ? 0 : index;
+}
+
+// meshLight_t::illumSample with sampleSurface and triangle_t::sample
+// (meshlight.cc:80-138, triangle.cc:156-167), in source order with the
+// reference's types. tri: the sampled triangle's index in light order. A
+// primNum >= count ("Sampling error": s1 above cdf[n] = 1, which no Halton
+// value reaches) leaves the reference's point unset; here it refuses.
+__device__ __forceinline__ bool mesh_illum(const DLight& L, const DMeshLight& ML, v3 P, float s1, float s2, v3& ldir,
+                                           float& tmax, float& pdf, int& tri) {
+  const int primNum = mesh_dsample(ML.cdf, ML.n, s1);
+  if (primNum >= ML.n) return false;
+  tri = primNum;
+  float ss1, delta = ML.cdf[primNum + 1];
+  if (primNum > 0) {
+    const float c0 = ML.cdf[primNum];
+    delta -= c0;
+    ss1 = (s1 - c0) / delta;
+  } else {
+    ss1 = s1 / delta;
+  }
+  const float* tv = ML.verts + 9 * (size_t)primNum;
+  const float su1 = sqrtf(ss1);
+  const float u = 1.f - su1;
+  const float v = s2 * su1;
+  const float w = 1.f - u - v;
+  const v3 p = V3((u * tv[0] + v * tv[3]) + w * tv[6], (u * tv[1] + v * tv[4]) + w * tv[7],
+                  (u * tv[2] + v * tv[5]) + w * tv[8]);
+  const v3 n = ld3(ML.nrm + 3 * (size_t)primNum);
+  v3 l = vsub(p, P);
+  const float dist_sqr = l.x * l.x + l.y * l.y + l.z * l.z;
+  const float dist = sqrtf(dist_sqr);
+  if (dist <= 0.0f) return false;
+  const float id = 1.f / dist;
+  l = V3(l.x * id, l.y * id, l.z * id);
+  float cos_angle = -vdot(l, n);
+  if (cos_angle <= 0.f) {  // no light behind a single-sided mesh
+    if (L.double_sided) cos_angle = -cos_angle;
+    else return false;
+  }
+  tmax = dist;
+  ldir = l;
+  const float amc = L.area * cos_angle;
+  pdf = (float)((double)dist_sqr * YK_PI_D / (double)((amc == 0.f) ? 1e-8f : amc));
+  return true;
+}
+
+// meshLight_t::intersect's kd-tree stack: one lane's pending exits of the
+// light's own tree, in private (scratch) memory. A valid traversal holds at
+// most depth_cap = depth + 2 entries and a descent pushes at index <=
+// depth_cap, so YK_MESH_LIGHT_MAX_DEPTH + 3 entries hold every tree
+// yk_device_upload lets through; the index is clamped all the same.
+constexpr int kMeshStack = YK_MESH_LIGHT_MAX_DEPTH + 3;
+struct MeshStack {
+  uint2* e;
+  __device__ __forceinline__ void push(int sp, uint2 v) const {
+    if ((unsigned)sp < (unsigned)kMeshStack) e[sp] = v;
+  }
+  __device__ __forceinline__ uint2 pop(int sp) const {
+    return (unsigned)sp < (unsigned)kMeshStack ? e[sp] : make_uint2(0u, 3u << 30);
+  }
+};
+
+// meshLight_t::intersect (meshlight.cc:180-203): triKdTree_t::Intersect on the
+// light's own tree -- the scene traversal's per-lane step (trav_begin /
+// trav_step<true>: acceptance t < Z && t >= tmin, first-wins leaf order,
+// kdtree.cc:766-800) on the light's node, leaf and record arrays -- with
+// bRay's tmin = MIN_RAYDIST and unbounded tmax (mcintegrator.cc:165-175),
+// then the sidedness rule and ipdf. The lanes of a wave hold different
+// shading points but walk the same small tree, which stays in cache. Bounds
+// as trace_body has them: trav_step ends a descent longer than depth_cap and
+// checks the popped node and the stack index; a traversal of a valid tree
+// reaches each leaf once, so more than nnodes steps end the ray as well.
+__device__ __forceinline__ bool mesh_hit(const DLight& L, const DMeshLight& ML, v3 from, v3 dir, float& t,
+                                         float& ipdf, int& tri) {
+  DScene LS{};  // the light's tree as a scene of its own; what the closest-hit step does not read stays zero
+  LS.tris = ML.tris;
+  LS.nodes = ML.nodes;
+  LS.leaf = ML.leaf;
+  for (int k = 0; k < 6; ++k) LS.bound[k] = ML.bound[k];
+  LS.nnodes = ML.nnodes;
+  LS.depth_cap = ML.depth_cap;
+  yk_ray r;
+  r.from[0] = from.x, r.from[1] = from.y, r.from[2] = from.z;
+  r.dir[0] = dir.x, r.dir[1] = dir.y, r.dir[2] = dir.z;
+  r.tmin = YK_MIN_RAYDIST;
+  r.tmax = -1.0f;
+  Trav st;
+  if (!trav_begin<true>(LS, st, r)) return false;
+  uint2 ents[kMeshStack];
+  MeshStack stk{ents};
+  unsigned nn = 0, nt = 0, steps = 0;
+  bool occ = false;
+  while (!trav_step<true, false>(LS, st, stk, nn, nt, occ))
+    if (++steps > ML.nnodes) return false;
+  if (st.prim < 0 || st.prim >= ML.n) return false;  // miss, or the watchdog's -2
+  tri = st.prim;
+  t = st.Z;
+  const v3 n = ld3(ML.nrm + 3 * (size_t)st.prim);
+  float cos_angle = vdot(dir, vneg(n));
+  if (cos_angle <= 0.f) {
+    if (L.double_sided) cos_angle = fabsf(cos_angle);
+    else return false;
+  }
+  ipdf = (float)((double)((1.f / (t * t)) * L.area * cos_angle) * YK_1_PI_D);
+  return true;
+}
+
 // pointLight_t::illuminate (pointlight.cc:60-75) / directionalLight_t::
 // illuminate (directional.cc:77-96), compiled forms: |v|^2 as (x*x + y*y) + z*z,
 // 1/dist and 1/dist^2 as separate divisions; col = color * (1/dist^2).
@@ -2707,22 +2853,27 @@ __device__ __forceinline__ void put_org(const Batch& B, long long c, v3 P) {
 // light_t::diracLight(): point, directional and hard spot lights take
 // doLightEstimation's one-ray branch, the others its sample loops
 __device__ __forceinline__ bool light_sampled(const DLight& L) {
-  return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.soft != 0;
+  return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.type == YK_LIGHT_MESH || L.soft != 0;
 }
 
 template <bool DIFF, int KIND>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
-                                           unsigned loffs, unsigned long long& traced);
+                                           unsigned loffs, unsigned long long& traced,
+                                           const DMeshLight* ml = nullptr);
 
 // mcIntegrator_t::doLightEstimation, mcintegrator.cc:73-195, split
 // at its isShadowed calls: every shadow ray it would trace is written to its
 // slot with the contribution it adds when unoccluded. Returns #rays; sets bit
 // k of `traced` (k < 64) for each slot that holds a ray.
-template <bool DIFF = false, bool XL = false>
+// XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light) or
+// kXLMesh (it holds a mesh light; ml = DScene::ml): see shade_primary_fn
+constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2;
+template <bool DIFF = false, int XL = kXLNone>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
-                                         unsigned long long& traced, const DMat* mats = c_mats) {
+                                         unsigned long long& traced, const DMat* mats = c_mats,
+                                         const DMeshLight* ml = nullptr) {
   const DLight& L = c_lights[li];
   const DMat& M = mats[sp.mat];
   const c3 black = C3(0.f, 0.f, 0.f);
@@ -2730,6 +2881,8 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
   // outside the sample loops
   if (L.type == YK_LIGHT_AREA)
     return gen_sampled<DIFF, YK_LIGHT_AREA>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  if (XL == kXLMesh && L.type == YK_LIGHT_MESH)
+    return gen_sampled<DIFF, YK_LIGHT_MESH>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced, ml + L.mesh);
   if (XL && L.type == YK_LIGHT_SPHERE)
     return gen_sampled<DIFF, YK_LIGHT_SPHERE>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
   if (XL && L.soft)
@@ -2739,7 +2892,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
     v3 ldir;
     float ltmax;
     c3 lc;
-    if (!dirac_illum<XL>(L, sp.P, ldir, ltmax, lc)) {
+    if (!dirac_illum<XL != kXLNone>(L, sp.P, ldir, ltmax, lc)) {
       put_slot(B, slot, 0, black);
       return 0;
     }
@@ -2762,7 +2915,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 // doLightEstimation's branch for lights with illumSample (mcintegrator.cc:
 // 101-193). Three things depend on the light's kind (KIND, a YK_LIGHT_*):
 // its sample function, its intersect function and ls.col / lcol -- the
-// colour as is for area and sphere lights, the colour times the cone's
+// colour as is for area, sphere and mesh lights, the colour times the cone's
 // falloff cv for a soft spot (kept in the slot's aux record under
 // transparent shadows, which filter the colour first). A sphere light's
 // canIntersect() is false (spherelight.cc:49): no MIS weight on its light
@@ -2770,7 +2923,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 template <bool DIFF, int KIND>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
-                                           unsigned loffs, unsigned long long& traced) {
+                                           unsigned loffs, unsigned long long& traced, const DMeshLight* ml) {
   constexpr bool CAN_INTERSECT = KIND != YK_LIGHT_SPHERE;
   const c3 black = C3(0.f, 0.f, 0.f);
   const int n = L.samples;
@@ -2787,7 +2940,9 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
     v3 ldir;
     float ltmax, lpdf, cv = 1.f;
     bool lit;
+    int tri;
     if (KIND == YK_LIGHT_AREA) lit = light_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
+    else if (KIND == YK_LIGHT_MESH) lit = mesh_illum(L, *ml, sp.P, s1, s2, ldir, ltmax, lpdf, tri);
     else if (KIND == YK_LIGHT_SPOT) lit = spot_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf, cv);
     else lit = sphere_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
     if (!lit) {
@@ -2834,14 +2989,16 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
     float bt, lightPdf, cv = 1.f;
     bool hit = false;
     if (spdf > 1e-6f) {
+      int tri;
       if (KIND == YK_LIGHT_AREA) hit = light_hit(L, sp.P, bdir, bt, lightPdf);
+      else if (KIND == YK_LIGHT_MESH) hit = mesh_hit(L, *ml, sp.P, bdir, bt, lightPdf, tri);
       else hit = spot_hit(L, sp.P, bdir, bt, lightPdf, cv);
     }
     if (!hit) {
       put_slot(B, slot, 0, black);
       continue;
     }
-    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0
+    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0; mesh: bt >= MIN_RAYDIST
     if (!(lightPdf > 1e-6f)) {
       put_slot(B, slot, SL_TRACED, black);
       continue;
@@ -2965,7 +3122,7 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // (spills of 124-200 B per lane) predates their register diet.
 // AO: direct lighting with ambient occlusion (gen_ao) -- an instantiation of
 // its own, so the others carry none of its code; A is read by it alone.
-template <bool DIFF, bool XL, bool AO>
+template <bool DIFF, int XL, bool AO>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
                                                        unsigned long long* __restrict__ qword, AOConst A) {
   // The material records in LDS: per-lane reads of constant memory (the
@@ -3021,7 +3178,7 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
         const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
         int k0 = 0;
         for (int l = 0; l < R.nlights; ++l) {
-          nr += gen_light<DIFF, XL>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats);
+          nr += gen_light<DIFF, XL>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats, S.ml);
           k0 += c_lights[l].nslots;
         }
         kend = k0;
@@ -3226,7 +3383,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
 // (pathtracer.cc:189-298): estimateOneDirectLight shadow rays, emission,
 // and the BSDF sample of the next segment. One thread per live path (entry
 // qi of the input bounce queue, owned by camera sample c).
-template <bool DIFF, bool XL>
+template <bool DIFF, int XL>
 __global__ void __launch_bounds__(bounce_block(DIFF))
 __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES))) k_shade_bounce(DScene S, Batch B, RenderConst R,
                                                       const unsigned long long* __restrict__ qin_word, int depth,
@@ -3286,8 +3443,8 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
         // compiler reads its record with scalar loads instead of per-lane
         // vector loads (which go through the texture path that limits this
         // kernel, PMC TD busy 0.9)
-        if (R.nlights == 1) nr = gen_light<DIFF, XL>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced);
-        else nr = gen_light<DIFF, XL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
+        if (R.nlights == 1) nr = gen_light<DIFF, XL>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced, c_mats, S.ml);
+        else nr = gen_light<DIFF, XL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced, c_mats, S.ml);
         kend = c_lights[lnum].nslots;
         if (nr) put_org(B, c, sp.P);
         if (R.nlights > 1) B.lsel[c] = lnum;  // one light: the resolve knows it is light 0
@@ -3357,16 +3514,25 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
 // spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
 // therefore run kernels that leave that code out (XL = false), as scenes
 // with plain diffuse materials leave out the component loop.
-inline auto shade_primary_fn(bool diff, bool xl, bool ao) {
+// A mesh light (kXLMesh) adds its own instantiations on top of the spot and
+// sphere code: meshLight_t::intersect walks the light's kd-tree per BSDF-half
+// sample with a per-lane stack in scratch memory (MeshStack), which no other
+// scene pays for.
+inline auto shade_primary_fn(bool diff, int xl, bool ao) {
+  if (xl == kXLMesh) {
+    if (ao) return diff ? k_shade_primary<true, kXLMesh, true> : k_shade_primary<false, kXLMesh, true>;
+    return diff ? k_shade_primary<true, kXLMesh, false> : k_shade_primary<false, kXLMesh, false>;
+  }
   if (ao)
-    return xl ? (diff ? k_shade_primary<true, true, true> : k_shade_primary<false, true, true>)
-              : (diff ? k_shade_primary<true, false, true> : k_shade_primary<false, false, true>);
-  return xl ? (diff ? k_shade_primary<true, true, false> : k_shade_primary<false, true, false>)
-            : (diff ? k_shade_primary<true, false, false> : k_shade_primary<false, false, false>);
+    return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, true> : k_shade_primary<false, kXLSpotSphere, true>)
+              : (diff ? k_shade_primary<true, kXLNone, true> : k_shade_primary<false, kXLNone, true>);
+  return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, false> : k_shade_primary<false, kXLSpotSphere, false>)
+            : (diff ? k_shade_primary<true, kXLNone, false> : k_shade_primary<false, kXLNone, false>);
 }
-inline auto shade_bounce_fn(bool diff, bool xl) {
-  return xl ? (diff ? k_shade_bounce<true, true> : k_shade_bounce<false, true>)
-            : (diff ? k_shade_bounce<true, false> : k_shade_bounce<false, false>);
+inline auto shade_bounce_fn(bool diff, int xl) {
+  if (xl == kXLMesh) return diff ? k_shade_bounce<true, kXLMesh> : k_shade_bounce<false, kXLMesh>;
+  return xl ? (diff ? k_shade_bounce<true, kXLSpotSphere> : k_shade_bounce<false, kXLSpotSphere>)
+            : (diff ? k_shade_bounce<true, kXLNone> : k_shade_bounce<false, kXLNone>);
 }
 
 // pathCol += lcol*throughput; throughput *= scol of the next segment. One
@@ -4464,7 +4630,12 @@ struct yk_device {
   DScene S{};
   int ntris = 0, max_depth = 0, nlights = 0, sum_light_slots = 0;
   bool spec = false;  // some material has SPECULAR|FILTER components: recursion pipeline
-  bool xl_lights = false;  // the scene holds a spot or sphere light (shading kernels' XL instantiation)
+  int xl_lights = 0;  // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light (shading kernels' XL instantiation)
+  // mesh lights: one record per light in DScene::ml, its arrays packed in three buffers
+  DBuf<DMeshLight> ml_recs;
+  DBuf<float> ml_f;
+  DBuf<uint2> ml_nodes;
+  DBuf<uint32_t> ml_leaf;
   bool diff_only = false;  // every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>)
   yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
   void* abort_user = nullptr;
@@ -5318,10 +5489,66 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
       if (!(m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on)))
         d->diff_only = false;
   }
+  // mesh lights: check every light's tree before anything of them is resident
+  // (a tree deeper than the shading kernels' per-lane stack is refused, not cut)
+  std::vector<int> ml_depth(S.light_states.size(), 0);
+  for (size_t i = 0; i < S.light_states.size(); ++i) {
+    if (S.light_kind[i] != YK_LIGHT_MESH) continue;
+    const MeshLight& ML = S.mesh_lights[i];
+    if (ML.areas.size() > (size_t)YK_MESH_LIGHT_MAX_TRIS)
+      return set_error(YK_ERR_UNSUPPORTED, "mesh light has more than YK_MESH_LIGHT_MAX_TRIS triangles");
+    std::string lerr;
+    ml_depth[i] = tree_depth(ML.tree.nodes.data(), ML.tree.nodes.size() / 2, ML.tree.leaf_prims.size(),
+                             ML.areas.size(), &lerr);
+    if (ml_depth[i] < 0) return set_error(YK_ERR_ARG, "yk_device_upload: mesh light: " + lerr);
+    if (ml_depth[i] > YK_MESH_LIGHT_MAX_DEPTH)
+      return set_error(YK_ERR_UNSUPPORTED, "mesh light kd-tree deeper than YK_MESH_LIGHT_MAX_DEPTH");
+  }
   std::vector<DLight> lights;
   int sum_slots = 0;
+  std::vector<DMeshLight> ml_recs;  // pointers filled in below, once the buffers have their size
+  std::vector<float> ml_f;
+  std::vector<uint32_t> ml_nodes, ml_leaf;
+  std::vector<size_t> ml_off;  // per record: float, node (in nodes) and leaf offsets
   for (size_t i = 0; i < S.light_states.size(); ++i) {
-    if (S.light_kind[i] == YK_LIGHT_AREA) {
+    if (S.light_kind[i] == YK_LIGHT_MESH) {
+      const MeshLight& ML = S.mesh_lights[i];
+      const size_t n = ML.areas.size(), nn = ML.tree.nodes.size() / 2;
+      DLight D{};
+      D.type = YK_LIGHT_MESH;
+      D.samples = ML.params.samples;
+      D.nslots = 2 * ML.params.samples;  // light samples + BSDF (MIS) samples
+      D.area = ML.area;
+      D.double_sided = ML.params.double_sided ? 1 : 0;
+      D.mesh = (int)ml_recs.size();
+      for (int k = 0; k < 3; ++k) D.color[k] = ML.color[k];
+      lights.push_back(D);
+      DMeshLight R{};
+      std::memcpy(R.bound, ML.tree.bound, sizeof R.bound);
+      R.n = (int)n;
+      R.nnodes = (unsigned)nn;
+      R.depth_cap = (unsigned)ml_depth[i] + 2u;
+      R.nleaf = (unsigned)ML.tree.leaf_prims.size();
+      ml_recs.push_back(R);
+      ml_off.push_back(ml_f.size());
+      ml_off.push_back(ml_nodes.size() / 2);
+      ml_off.push_back(ml_leaf.size());
+      // floats: cdf (n + 1), verts (9n), records (kTriWords * n, + kRecPad), normals (3n)
+      ml_f.insert(ml_f.end(), ML.cdf.begin(), ML.cdf.end());
+      ml_f.insert(ml_f.end(), ML.verts.begin(), ML.verts.end());
+      for (size_t p = 0; p < n; ++p) {
+        const float* t = &ML.verts[9 * p];
+        const float rec[kTriWords] = {t[0],        t[1],        t[2],        t[3] - t[0], t[4] - t[1],
+                                      t[5] - t[2], t[6] - t[0], t[7] - t[1], t[8] - t[2]};
+        ml_f.insert(ml_f.end(), rec, rec + kTriWords);
+      }
+      ml_f.insert(ml_f.end(), kRecPad, 0.f);
+      ml_f.insert(ml_f.end(), ML.normals.begin(), ML.normals.end());
+      ml_nodes.insert(ml_nodes.end(), ML.tree.nodes.begin(), ML.tree.nodes.end());
+      ml_nodes.insert(ml_nodes.end(), 2, 0u);  // one padding node for the node-pair loads
+      ml_leaf.insert(ml_leaf.end(), ML.tree.leaf_prims.begin(), ML.tree.leaf_prims.end());
+      ml_leaf.push_back(0u);
+    } else if (S.light_kind[i] == YK_LIGHT_AREA) {
       lights.push_back(make_light(S.light_states[i]));
     } else if (S.light_kind[i] == YK_LIGHT_SPOT) {
       lights.push_back(make_spot_light(S.spot_states[i]));
@@ -5333,9 +5560,33 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
     }
     sum_slots += lights.back().nslots;
   }
-  d->xl_lights = false;
+  d->xl_lights = kXLNone;
   for (const DLight& L : lights)
-    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) d->xl_lights = true;
+    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) d->xl_lights = kXLSpotSphere;
+  d->S.ml = nullptr;
+  if (!ml_recs.empty()) {
+    d->xl_lights = kXLMesh;
+    d->ml_f.ensure(ml_f.size());
+    d->ml_nodes.ensure(ml_nodes.size() / 2);
+    d->ml_leaf.ensure(ml_leaf.size());
+    d->ml_recs.ensure(ml_recs.size());
+    for (size_t k = 0; k < ml_recs.size(); ++k) {
+      DMeshLight& R = ml_recs[k];
+      const size_t n = (size_t)R.n;
+      const float* f = d->ml_f.p + ml_off[3 * k];
+      R.cdf = f;
+      R.verts = f + (n + 1);
+      R.tris = R.verts + 9 * n;
+      R.nrm = R.tris + kTriWords * n + kRecPad;
+      R.nodes = d->ml_nodes.p + ml_off[3 * k + 1];
+      R.leaf = d->ml_leaf.p + ml_off[3 * k + 2];
+    }
+    HIPCHK(hipMemcpy(d->ml_f.p, ml_f.data(), ml_f.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->ml_nodes.p, ml_nodes.data(), ml_nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->ml_leaf.p, ml_leaf.data(), ml_leaf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d->ml_recs.p, ml_recs.data(), ml_recs.size() * sizeof(DMeshLight), hipMemcpyHostToDevice));
+    d->S.ml = d->ml_recs.p;
+  }
   d->sum_light_slots = sum_slots;
   d->lights_host = lights;
   d->pm_ready = false;

@@ -204,6 +204,86 @@ int yk_scene_add_light(yk_scene* s, const yk_light* l) {
   YK_GUARD_END
 }
 
+// what scene_t::getMesh hands meshLight_t::init as a triangleObject_t
+// (scene.cc:709-713): a TRIM mesh, not an instance
+static int mesh_light_target(const yk::Scene& S, int32_t id, const char* who) {
+  if (id < 1 || id > (int32_t)S.meshes.size())
+    return set_error(YK_ERR_ARG, std::string(who) + ": unknown object id " + std::to_string(id));
+  const yk::Mesh& m = S.meshes[(size_t)id - 1];
+  if (m.instance_of >= 0)
+    return set_error(YK_ERR_UNSUPPORTED, std::string(who) + ": object " + std::to_string(id) + " is an instance");
+  if (m.type != YK_MESH_TRIM)
+    return set_error(YK_ERR_UNSUPPORTED, std::string(who) + ": object " + std::to_string(id) + " is a VTRIM mesh");
+  return YK_OK;
+}
+
+int yk_scene_add_mesh_light(yk_scene* s, const yk_mesh_light* l, const int32_t* obj_ids, int32_t nobj) {
+  if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_mesh_light: NULL argument");
+  if (nobj < 1 || !obj_ids) return set_error(YK_ERR_ARG, "yk_scene_add_mesh_light: empty object list");
+  if (l->samples < 1) return set_error(YK_ERR_ARG, "mesh light needs samples >= 1");
+  if (!std::isfinite(l->color[0]) || !std::isfinite(l->color[1]) || !std::isfinite(l->color[2]) ||
+      !std::isfinite(l->power))
+    return set_error(YK_ERR_ARG, "mesh light needs a finite colour and power");
+  int64_t ntris = 0;
+  for (int32_t i = 0; i < nobj; ++i) {
+    if (const int rc = mesh_light_target(s->s, obj_ids[i], "yk_scene_add_mesh_light")) return rc;
+    for (int32_t j = 0; j < i; ++j)
+      if (obj_ids[j] == obj_ids[i])
+        return set_error(YK_ERR_ARG, "yk_scene_add_mesh_light: object id " + std::to_string(obj_ids[i]) + " repeated");
+    ntris += (int64_t)(s->s.meshes[(size_t)obj_ids[i] - 1].faces.size() / 3);
+  }
+  if (ntris > YK_MESH_LIGHT_MAX_TRIS)
+    return set_error(YK_ERR_UNSUPPORTED, "mesh light has more than YK_MESH_LIGHT_MAX_TRIS triangles");
+  YK_GUARD_BEGIN
+  s->s.add_mesh_light(*l, obj_ids, nobj);
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_mesh_light(const yk_scene* s, int32_t i, yk_mesh_light* out, int32_t* obj_ids, int32_t cap,
+                            int32_t* nobj_out) {
+  if (!s || i < 0 || i >= (int32_t)s->s.mesh_lights.size() || cap < 0 || (cap > 0 && !obj_ids))
+    return set_error(YK_ERR_ARG, "yk_scene_get_mesh_light: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_MESH) return set_error(YK_ERR_STATE, "light is not a mesh light");
+  const yk::MeshLight& L = s->s.mesh_lights[i];
+  if (out) *out = L.params;
+  for (int32_t k = 0; k < cap && k < (int32_t)L.obj_ids.size(); ++k) obj_ids[k] = L.obj_ids[k];
+  if (nobj_out) *nobj_out = (int32_t)L.obj_ids.size();
+  return YK_OK;
+}
+
+int yk_scene_get_mesh_light_state(const yk_scene* s, int32_t i, yk_mesh_light_state* out, float* cdf,
+                                  float* tri_areas, int32_t cap_tris) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.mesh_lights.size() || cap_tris < 0)
+    return set_error(YK_ERR_ARG, "yk_scene_get_mesh_light_state: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_MESH) return set_error(YK_ERR_STATE, "light is not a mesh light");
+  if (!s->s.built) return set_error(YK_ERR_STATE, "yk_scene_get_mesh_light_state: scene not built");
+  const yk::MeshLight& L = s->s.mesh_lights[i];
+  std::memset(out, 0, sizeof *out);
+  for (int k = 0; k < 3; ++k) out->color[k] = L.color[k];
+  out->samples = L.params.samples;
+  out->double_sided = L.params.double_sided;
+  out->area = L.area;
+  out->inv_area = L.inv_area;
+  out->ntris = (int32_t)L.areas.size();
+  out->tree_depth = L.tree.max_depth;
+  out->tree_nodes = (int32_t)(L.tree.nodes.size() / 2);
+  const int32_t n = std::min(cap_tris, out->ntris);
+  if (cdf && n > 0) std::memcpy(cdf, L.cdf.data(), ((size_t)n + 1) * sizeof(float));
+  if (tri_areas && n > 0) std::memcpy(tri_areas, L.areas.data(), (size_t)n * sizeof(float));
+  return YK_OK;
+}
+
+int yk_scene_set_mesh_light_color(yk_scene* s, int32_t i, const float* rgb) {
+  if (!s || !rgb || i < 0 || i >= (int32_t)s->s.mesh_lights.size())
+    return set_error(YK_ERR_ARG, "yk_scene_set_mesh_light_color: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_MESH) return set_error(YK_ERR_STATE, "light is not a mesh light");
+  if (!std::isfinite(rgb[0]) || !std::isfinite(rgb[1]) || !std::isfinite(rgb[2]))
+    return set_error(YK_ERR_ARG, "mesh light needs a finite colour");
+  for (int k = 0; k < 3; ++k) s->s.mesh_lights[i].color[k] = rgb[k];
+  return YK_OK;
+}
+
 int yk_scene_add_area_light_state(yk_scene* s, const yk_area_light_state* l) {
   if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_area_light_state: NULL argument");
   if (l->samples < 1) return set_error(YK_ERR_ARG, "area light needs samples >= 1");
@@ -349,6 +429,15 @@ int yk_scene_build(yk_scene* s) {
     for (const yk::Mesh& m : s->s.meshes)
       if (m.instance_of >= 0)  // scene_t::addInstance refuses outside triangle mode (scene.cc:985)
         return set_error(YK_ERR_UNSUPPORTED, "yk_scene_build: universal mode has no instances");
+  for (const yk::MeshLight& L : s->s.mesh_lights) {  // a target retyped after yk_scene_add_mesh_light
+    int64_t ntris = 0;
+    for (const int32_t id : L.obj_ids) {
+      if (const int rc = mesh_light_target(s->s, id, "yk_scene_build: mesh light")) return rc;
+      ntris += (int64_t)(s->s.meshes[(size_t)id - 1].faces.size() / 3);
+    }
+    if (ntris > YK_MESH_LIGHT_MAX_TRIS)
+      return set_error(YK_ERR_UNSUPPORTED, "mesh light has more than YK_MESH_LIGHT_MAX_TRIS triangles");
+  }
   YK_GUARD_BEGIN
   s->s.finalize();
   return YK_OK;

@@ -46,9 +46,10 @@ __global__ void k_qmc_probe(int fn, const void* in, const uint32_t* in2, long lo
 }
 
 // yk_debug_light_probe: the shading kernels' own light functions (dirac_illum,
-// light_illum / spot_illum / sphere_illum, light_hit / spot_hit / sphere_hit)
-// on light li of the bound constants; col as gen_light / gen_sampled form it
-__global__ void k_light_probe(int li, int fn, const float* in, long long n, float* out) {
+// light_illum / spot_illum / sphere_illum / mesh_illum, light_hit / spot_hit /
+// sphere_hit / mesh_hit) on light li of the bound constants (ml: the handle's
+// mesh-light records); col as gen_light / gen_sampled form it
+__global__ void k_light_probe(int li, int fn, const float* in, long long n, float* out, const DMeshLight* ml) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const DLight& L = c_lights[li];
@@ -57,6 +58,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   const c3 lcol = C3(L.color[0], L.color[1], L.color[2]);
   v3 dir = V3(0.f, 0.f, 0.f);
   float tmax = 0.f, pdf = 0.f, cv = 1.f;
+  int tri = 0;
   c3 col = C3(0.f, 0.f, 0.f);
   if (fn == YK_LIGHT_PROBE_ILLUMINATE) {
     const bool dirac = L.type == YK_LIGHT_POINT || L.type == YK_LIGHT_DIRECTIONAL || L.type == YK_LIGHT_SPOT;
@@ -67,6 +69,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
     if (L.type == YK_LIGHT_AREA) ok = light_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf);
     else if (L.type == YK_LIGHT_SPOT) ok = spot_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf, cv);
     else if (L.type == YK_LIGHT_SPHERE) ok = sphere_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf);
+    else if (L.type == YK_LIGHT_MESH) ok = mesh_illum(L, ml[L.mesh], ld3(x), x[3], x[4], dir, tmax, pdf, tri);
     if (!ok) return;
     col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
   } else {
@@ -76,6 +79,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
     if (L.type == YK_LIGHT_AREA) ok = light_hit(L, ld3(x), ld3(x + 3), t, pdf);
     else if (L.type == YK_LIGHT_SPOT) ok = spot_hit(L, ld3(x), ld3(x + 3), t, pdf, cv);
     else if (L.type == YK_LIGHT_SPHERE) ok = sphere_hit(L, ld3(x), ld3(x + 3), pdf);
+    else if (L.type == YK_LIGHT_MESH) ok = mesh_hit(L, ml[L.mesh], ld3(x), ld3(x + 3), t, pdf, tri);
     if (!ok) return;
     col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
     o[0] = 1.f;
@@ -85,6 +89,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
     o[4] = col.g;
     o[5] = col.b;
     o[6] = pdf;
+    o[YK_LIGHT_PROBE_TRI] = (float)tri;
     return;
   }
   o[0] = 1.f;
@@ -96,6 +101,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   o[6] = col.g;
   o[7] = col.b;
   o[8] = pdf;
+  o[YK_LIGHT_PROBE_TRI] = (float)tri;
 }
 
 // yk_debug_camera_rays: cam_shoot of the bound camera's kind, the function
@@ -164,7 +170,7 @@ extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t f
   dout.ensure((size_t)n * YK_LIGHT_PROBE_STRIDE);
   HIPCHK(hipMemcpy(din.p, in, (size_t)n * in_f * sizeof(float), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_light_probe, dim3(grid_for(n)), dim3(256), 0, d->stream, (int)light_index, (int)fn,
-                     (const float*)din.p, (long long)n, dout.p);
+                     (const float*)din.p, (long long)n, dout.p, d->S.ml);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipMemcpy(out, dout.p, (size_t)n * YK_LIGHT_PROBE_STRIDE * sizeof(float), hipMemcpyDeviceToHost));

@@ -123,6 +123,30 @@ class Scene:
                        from_=A.f3(*from_), radius=radius)
         A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
 
+    def add_mesh_light(self, obj_ids, color=(1, 1, 1), power=1.0, samples=4, double_sided=False):
+        """meshlight (meshlight.cc:221-236) over the triangles of the TRIM meshes obj_ids (one id or a
+        list), concatenated in the order given"""
+        ids = np.ascontiguousarray(np.atleast_1d(obj_ids), dtype=np.int32)
+        l = A.yk_mesh_light(A.f3(*color), power, samples, int(double_sided))
+        A.check(A.lib().yk_scene_add_mesh_light(self._p, C.byref(l), ids.ctypes.data_as(A.i32p), len(ids)))
+
+    def mesh_light(self, i):
+        """(yk_mesh_light, [object ids]) of mesh light i"""
+        l, n = A.yk_mesh_light(), C.c_int32()
+        A.check(A.lib().yk_scene_get_mesh_light(self._p, i, C.byref(l), None, 0, C.byref(n)))
+        ids = np.zeros(max(n.value, 1), np.int32)
+        A.check(A.lib().yk_scene_get_mesh_light(self._p, i, None, ids.ctypes.data_as(A.i32p), n.value, None))
+        return l, [int(x) for x in ids[:n.value]]
+
+    def mesh_light_state(self, i):
+        """(yk_mesh_light_state, cdf (ntris + 1), triangle areas (ntris)) of mesh light i of a built scene"""
+        st = A.yk_mesh_light_state()
+        A.check(A.lib().yk_scene_get_mesh_light_state(self._p, i, C.byref(st), None, None, 0))
+        cdf, areas = np.zeros(st.ntris + 1, np.float32), np.zeros(st.ntris, np.float32)
+        A.check(A.lib().yk_scene_get_mesh_light_state(self._p, i, C.byref(st), cdf.ctypes.data_as(A.fp),
+                                                      areas.ctypes.data_as(A.fp), st.ntris))
+        return st, cdf, areas
+
     def set_background(self, color, power=1.0):
         """constant background (textureback.cc:206-218, ibl off); None removes it"""
         if color is None:
@@ -188,13 +212,15 @@ class Scene:
         A.check(A.lib().yk_scene_add_sphere_light_state(self._p, C.byref(st)))
 
     def light_states(self):
-        """Per light: yk_area_light_state, yk_dirac_light_state, yk_spot_light_state
-        or yk_sphere_light_state (each getter answers YK_ERR_STATE for the other kinds)."""
+        """Per light: yk_area_light_state, yk_dirac_light_state, yk_spot_light_state,
+        yk_sphere_light_state or yk_mesh_light_state (each getter answers YK_ERR_STATE for
+        the other kinds; a mesh light's state needs a built scene)."""
         L = A.lib()
         getters = ((A.yk_area_light_state, L.yk_scene_get_area_light_state),
                    (A.yk_dirac_light_state, L.yk_scene_get_dirac_light_state),
                    (A.yk_spot_light_state, L.yk_scene_get_spot_light_state),
-                   (A.yk_sphere_light_state, L.yk_scene_get_sphere_light_state))
+                   (A.yk_sphere_light_state, L.yk_scene_get_sphere_light_state),
+                   (A.yk_mesh_light_state, lambda p, k, m: L.yk_scene_get_mesh_light_state(p, k, m, None, None, 0)))
         out = []
         for k in range(self.info().nlights):
             for cls, get in getters:

@@ -67,7 +67,12 @@ typedef struct yk_material {
 } yk_material;
 enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 
-enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2, YK_LIGHT_SPOT = 3, YK_LIGHT_SPHERE = 4 };
+/* YK_LIGHT_MESH is the kind yk_scene_get_light and the device state report for
+ * a mesh light; it is added with yk_scene_add_mesh_light, and
+ * yk_scene_add_light answers YK_ERR_UNSUPPORTED for it (yk_light has no room
+ * for object ids). */
+enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2, YK_LIGHT_SPOT = 3, YK_LIGHT_SPHERE = 4,
+       YK_LIGHT_MESH = 5 };
 typedef struct yk_light {
   int32_t type;
   /* area: areaLight_t::factory, arealight.cc:171-192 */
@@ -98,6 +103,23 @@ typedef struct yk_light {
   float shadow_fuzzyness;
   int32_t photon_only;
 } yk_light;
+
+/* meshlight: meshLight_t::factory (meshlight.cc:221-236): color [1,1,1],
+ * power [1], samples [4], double_sided [0]; a zero-initialised struct must set
+ * them. Its "object" is the obj_ids list of yk_scene_add_mesh_light. The
+ * stored colour is color * (float)power * M_PI in the factory's types. */
+typedef struct yk_mesh_light {
+  float color[3];
+  float power;
+  int32_t samples;
+  int32_t double_sided;
+} yk_mesh_light;
+/* Device limits of one mesh light (YK_ERR_UNSUPPORTED from yk_scene_build
+ * above the first, from yk_device_upload above the second; never a truncated
+ * light): triangles in its list, and depth of its private kd-tree -- the
+ * per-lane traversal stack of the shading kernels holds depth + 3 entries.
+ * triKdTree_t's own depth limit for 65536 triangles is 25. */
+enum { YK_MESH_LIGHT_MAX_TRIS = 65536, YK_MESH_LIGHT_MAX_DEPTH = 29 };
 
 /* perspectiveCam_t bokeh shapes and bias (perspectiveCamera.h:33-34) */
 enum { YK_BOKEH_DISK1 = 0, YK_BOKEH_DISK2 = 1, YK_BOKEH_TRI = 3, YK_BOKEH_SQR = 4, YK_BOKEH_PENTA = 5,
@@ -341,6 +363,24 @@ int yk_scene_set_mesh_base(yk_scene* s, int32_t obj_id);
  * are flattened with the reference's vertex / normal transform arithmetic. */
 int yk_scene_add_instance(yk_scene* s, int32_t base_obj_id, const float* obj_to_world, int32_t* obj_id_out);
 int yk_scene_add_light(yk_scene* s, const yk_light* l);
+/* meshLight_t over the triangles of the nobj TRIM meshes obj_ids, concatenated
+ * in the order given (one reference object may arrive as several yk meshes,
+ * one per run of equal material): triangleObject_t::getPrimitives order. The
+ * light samples and intersects those triangles; the meshes themselves stay
+ * ordinary scene geometry with their own material (a light_mat, usually).
+ * YK_ERR_ARG: an unknown or repeated id, an empty list, samples < 1, a
+ * non-finite colour or power; from yk_scene_build, a list whose total area is
+ * zero. YK_ERR_UNSUPPORTED: a VTRIM mesh or an instance id (scene_t::getMesh
+ * hands meshLight_t::init neither as a triangleObject_t), also when the mesh
+ * is retyped after the call (found by yk_scene_build), and a list above
+ * YK_MESH_LIGHT_MAX_TRIS. Photon emission of a mesh light is not on the path:
+ * yk_photon_build refuses a scene that holds one. */
+int yk_scene_add_mesh_light(yk_scene* s, const yk_mesh_light* l, const int32_t* obj_ids, int32_t nobj);
+/* parameters and id list of mesh light i (YK_ERR_STATE for another kind);
+ * at most cap ids are written, *nobj_out is the list's length; out, obj_ids
+ * and nobj_out may be NULL */
+int yk_scene_get_mesh_light(const yk_scene* s, int32_t i, yk_mesh_light* out, int32_t* obj_ids, int32_t cap,
+                            int32_t* nobj_out);
 /* YK_ERR_UNSUPPORTED for an unknown type; YK_ERR_ARG for a non-finite or
  * non-positive scale (orthographic) or angle (angular), a non-finite or
  * negative max_angle (angular), and an aperture on an orthographic or angular
@@ -492,6 +532,35 @@ int yk_scene_get_background(const yk_scene* s, float* rgb_out, int32_t* has_out)
 int yk_scene_set_camera_state(yk_scene* s, const yk_camera_state* c);
 int yk_scene_get_material_state(const yk_scene* s, int32_t i, yk_material_state* out);
 int yk_scene_get_area_light_state(const yk_scene* s, int32_t i, yk_area_light_state* out);
+/* meshLight_t members after init() (meshlight.cc:47-65), of a built scene:
+ * the colour with pi * power, area = (float)total and inv_area =
+ * (float)(1.0 / total) of the double running total of the float triangle
+ * areas. cdf (ntris + 1 floats, pdf1D_t::cdf as CumulateStep1dDF leaves it)
+ * and tri_areas (ntris floats, triangle_t::surfaceArea) may be NULL; at most
+ * cap_tris triangles' worth is written. tree_depth (triKdTree_t::maxDepth, the
+ * build's depth limit) and tree_nodes describe the light's own kd-tree
+ * (triKdTree_t(tris, n, -1, 1, 0.8, 0.33)). */
+typedef struct yk_mesh_light_state {
+  float color[3];
+  int32_t samples;
+  int32_t double_sided;
+  float area, inv_area;
+  int32_t ntris;
+  int32_t tree_depth, tree_nodes;
+} yk_mesh_light_state;
+int yk_scene_get_mesh_light_state(const yk_scene* s, int32_t i, yk_mesh_light_state* out, float* cdf,
+                                  float* tri_areas, int32_t cap_tris);
+/* meshLight_t::color of mesh light i as a live object holds it (pi * power
+ * already in it): replaces the colour yk_scene_add_mesh_light computed, so a
+ * plugin hands the member on bit for bit. yk_scene_get_light and
+ * yk_scene_get_mesh_light go on reporting the color and power the light was
+ * added with, which then no longer give the stored colour;
+ * yk_scene_get_mesh_light_state reports the stored one. The colour is read
+ * by yk_device_upload: the call does not touch the built scene, and a device
+ * that already holds the scene keeps the earlier colour until the next upload.
+ * YK_ERR_ARG for a non-finite colour, YK_ERR_STATE when light i is of another
+ * kind. */
+int yk_scene_set_mesh_light_color(yk_scene* s, int32_t i, const float* rgb);
 int yk_scene_get_camera_state(const yk_scene* s, yk_camera_state* out);
 
 /* ---- device ---- */

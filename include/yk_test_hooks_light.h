@@ -19,14 +19,17 @@ extern "C" {
  *                 (a spot light answers whether or not it has soft shadows);
  *                 ok = 0 for the others, as their illuminate() returns false
  *   ILLUM_SAMPLE  in: P[3], s1, s2     -> ok, dir[3], tmax, col[3], pdf
- *                 light_t::illumSample: area, spot and sphere lights
+ *                 light_t::illumSample: area, spot, sphere and mesh lights
  *   INTERSECT     in: from[3], dir[3]  -> ok, t, t_set, col[3], ipdf
- *                 light_t::intersect: area, spot and sphere lights; t_set = 0
+ *                 light_t::intersect: area, spot, sphere and mesh lights; t_set = 0
  *                 for a sphere light, whose intersect() never writes t
  *                 (spherelight.cc:134-149)
- * col is ls.col / lcol as doLightEstimation receives it. */
+ * col is ls.col / lcol as doLightEstimation receives it. A mesh light also
+ * writes out[YK_LIGHT_PROBE_TRI]: the index, in the light's own triangle
+ * order, of the triangle ILLUM_SAMPLE sampled or INTERSECT hit, as a float
+ * (0 for the other kinds). Its ILLUMINATE answers ok = 0. */
 enum { YK_LIGHT_PROBE_ILLUMINATE = 0, YK_LIGHT_PROBE_ILLUM_SAMPLE = 1, YK_LIGHT_PROBE_INTERSECT = 2 };
-enum { YK_LIGHT_PROBE_STRIDE = 12 };
+enum { YK_LIGHT_PROBE_STRIDE = 12, YK_LIGHT_PROBE_TRI = 11 };
 int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t fn, const float* in, int64_t n, float* out);
 
 #ifdef __cplusplus

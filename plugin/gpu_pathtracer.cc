@@ -31,6 +31,7 @@
 #include <cameras/orthographicCamera.h>
 #include <cameras/perspectiveCamera.h>
 #include <lights/arealight.h>
+#include <lights/meshlight.h>
 #include <materials/shinydiff.h>
 #include <yafraycore/meshtypes.h>
 #include <yafraycore/triangle.h>
@@ -125,6 +126,10 @@ YK_MEMBER(AlToX, areaLight_t, vector3d_t, toX)
 YK_MEMBER(AlToY, areaLight_t, vector3d_t, toY)
 YK_MEMBER(AlColor, areaLight_t, color_t, color)
 YK_MEMBER(AlSamples, areaLight_t, int, samples)
+YK_MEMBER(MlObjID, meshLight_t, unsigned int, objID)
+YK_MEMBER(MlDoubleSided, meshLight_t, bool, doubleSided)
+YK_MEMBER(MlColor, meshLight_t, color_t, color)
+YK_MEMBER(MlSamples, meshLight_t, int, samples)
 YK_MEMBER(CamPos, camera_t, point3d_t, position)
 YK_MEMBER(CamZ, camera_t, vector3d_t, camZ)
 YK_MEMBER(CamVto, camera_t, vector3d_t, vto)
@@ -202,6 +207,9 @@ struct SphereLightLayout : public light_t {
   unsigned int objID;
   float area, invArea;
 };
+// meshLight_t (meshlight.h:56-64) is declared in a header, but its members are
+// protected: read through YK_MEMBER like the area light's. Unverified: this
+// plugin is not compiled in this repository's setup.
 struct ConstBackgroundLayout : public background_t {
   color_t color;
 };
@@ -384,8 +392,35 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
         }
         continue;
       }
+      if (tn == "N7yafaray11meshLight_tE") {
+        // yk_photon_build refuses it as well: its emitPhoton is not on the path
+        if (params.integrator == YK_INTEGRATOR_PHOTON || params.caustic_type == YK_CAUSTIC_PHOTON ||
+            params.caustic_type == YK_CAUSTIC_BOTH ||
+            (params.integrator == YK_INTEGRATOR_DIRECT && params.dl_caustics != 0))
+          return unsupported("mesh lights run on the GPU path without photon maps only");
+        meshLight_t* ml = static_cast<meshLight_t*>(l);
+        auto mit = meshes.find(GET(*ml, MlObjID));
+        // scene_t::getMesh answers with objData_t::obj: a TRIM mesh's triangleObject_t
+        if (mit == meshes.end() || mit->second.type != TRIM || !mit->second.obj)
+          return unsupported("a mesh light on a VTRIM or missing mesh does not run on the GPU path");
+        auto ids = yk_ids.find(mit->second.obj);
+        if (ids == yk_ids.end() || ids->second.empty())
+          return unsupported("mesh light on a mesh the GPU path did not load");
+        yk_mesh_light d{};
+        put3(d.color, 1.f, 1.f, 1.f);
+        d.power = 1.f;
+        d.samples = GET(*ml, MlSamples);
+        d.double_sided = GET(*ml, MlDoubleSided) ? 1 : 0;
+        if (yk_scene_add_mesh_light(ys, &d, ids->second.data(), (int32_t)ids->second.size()) != YK_OK) return fail();
+        const color_t& mc = GET(*ml, MlColor);  // pi * power already in it
+        const float rgb[3] = {mc.R, mc.G, mc.B};
+        yk_scene_info inf;
+        if (yk_scene_info_get(ys, &inf) != YK_OK || yk_scene_set_mesh_light_color(ys, inf.nlights - 1, rgb) != YK_OK)
+          return fail();
+        continue;
+      }
       areaLight_t* al = dynamic_cast<areaLight_t*>(l);
-      if (!al) return unsupported("only area, point, directional, spot and sphere lights run on the GPU path");
+      if (!al) return unsupported("only area, point, directional, spot, sphere and mesh lights run on the GPU path");
       yk_area_light_state s{};
       const point3d_t& c = GET(*al, AlCorner);
       const vector3d_t &x = GET(*al, AlToX), &y = GET(*al, AlToY);
