@@ -1156,12 +1156,14 @@ struct RaySrc {
   unsigned omask, kshift, kstride;
 };
 
-template <bool CLOSEST, int NSEG, bool TS = false, bool BIG = false, bool UNI = false, int W = 1, bool SPLIT = false>
+template <bool CLOSEST, int NSEG, bool TS = false, bool BIG = false, bool UNI = false, int W = 1, bool SPLIT = false,
+          bool GROUP = false>
 __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned* __restrict__ idx,
                                            RayCount rc, yk_hit* __restrict__ hits, uint8_t* __restrict__ occl,
                                            unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,
                                            uint2* __restrict__ ovf, int ovf_depth, int refill_min,
                                            float* __restrict__ tsf = nullptr, int ts_depth = 0) {
+  static_assert(!GROUP || (CLOSEST && !TS && !UNI && !SPLIT), "the group hand-out serves the camera-ray closest-hit kernels");
   using KeyT = std::conditional_t<CLOSEST, unsigned long long, unsigned>;
   constexpr int R = W > 1 ? YK_SMALL_RING : (CLOSEST ? kStackLdsC : kStackLds);
   unsigned* otab;
@@ -1256,9 +1258,27 @@ __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned*
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
   constexpr unsigned kAll = (1u << NSEG) - 1u;
-  const unsigned seg_len = (unsigned)((n + NSEG - 1) / NSEG);
+  // (GROUP: whole groups per segment, so every chunk starts at a multiple of 64)
+  const unsigned seg_len = GROUP ? ((unsigned)((n + NSEG - 1) / NSEG) + 63u) & ~63u : (unsigned)((n + NSEG - 1) / NSEG);
   unsigned pool_next = 0, pool_end = 0;
   unsigned seg_done = 0;  // bit s: segment s has no chunks left
+  // Group hand-out (GROUP: the camera-ray launch, whose queue holds a pixel's
+  // samples consecutively). The pool hands out aligned groups of 64
+  // consecutive entries, and lane l only ever traces entry gbase + l: the
+  // lanes of a wave then walk almost the same nodes in the same iterations,
+  // and a wave-load touches few lines. The wave takes its next group once at
+  // most YK_CAMERA_T lanes are still active (0: lock-step); those stragglers
+  // keep their rays, and their entries of the new group (`pending`) start
+  // together when the last of them has finished. Idle lanes stay masked out.
+  // Lock-step is the default: headline +2.7 % against the lane-by-lane
+  // refill; thresholds of 2 and 4 kept half of that, 8 and more none of it
+  // (DESIGN §5).
+#ifndef YK_CAMERA_T
+#define YK_CAMERA_T 0
+#endif
+  unsigned gbase = 0;                // wave-uniform
+  unsigned long long pending = 0ull;  // entries gbase + l not started yet
+  bool drained = false;               // no group left anywhere (wave-uniform)
 
   // per-ray watchdog: a valid traversal visits every node at most once, so a
   // ray whose node visits exceed the tree's node count is looping through a
@@ -1274,7 +1294,66 @@ __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned*
   unsigned long long c_ref = 0, c_desc = 0, c_leaf = 0, c_pop = 0, c_t0 = clock64();
 #endif
   for (;;) {
-    const unsigned long long want = __ballot(rid < 0 && !exhausted);
+    if constexpr (GROUP) {
+      const unsigned long long act = __ballot(rid >= 0);
+      bool fresh = false;
+      if (pending == 0ull && !drained && __popcll(act) <= YK_CAMERA_T) {
+        if (pool_next >= pool_end && seg_done != kAll) {
+          // the chunk search of the refill below, at group granularity. (Its
+          // own copy, as the ray start further down: shared through local
+          // lambdas, every other trace kernel came out with other code and
+          // k_trace_closest with 16 B of scratch instead of 8.)
+#pragma unroll 1
+          for (unsigned k = 0; k < (unsigned)NSEG; ++k) {
+            const unsigned sgi = (xcc + k) % (unsigned)NSEG;
+            if (seg_done & (1u << sgi)) continue;
+            const unsigned long long s0 = (unsigned long long)sgi * seg_len;
+            const unsigned long long s1 = min(s0 + seg_len, (unsigned long long)n);
+            unsigned long long base = 0;
+            if (lane == 0) base = atomicAdd(work + 16 * sgi, (unsigned long long)kPoolChunk);
+            base = s0 + shfl_u64(base, 0);
+            if (base < s1) {
+              pool_next = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);
+              pool_end = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)min(base + kPoolChunk, s1));
+              break;
+            }
+            seg_done |= 1u << sgi;
+          }
+        }
+        if (pool_next < pool_end) {
+          const unsigned cnt = min(64u, pool_end - pool_next);  // a ragged last group
+          gbase = pool_next;
+          pending = ~0ull >> (64u - cnt);
+          pool_next += cnt;
+          fresh = true;
+        } else {
+          drained = true;
+        }
+      }
+      // the new group's idle lanes at once; the stragglers' entries together
+      const unsigned long long go = pending & ~act;
+      if (go != 0ull && (fresh || (pending & act) == 0ull)) {
+#ifdef YK_TRAV_STATS
+        s_refill++;
+#endif
+        const unsigned l = (unsigned)lane_fresh();
+        if ((go >> l) & 1ull) {
+          const int r = idx ? (int)idx[gbase + l] : (int)(gbase + l);
+          if (trav_begin<CLOSEST, TS, UNI>(S, st, src.rays[r])) {
+            rid = r;
+            ray_n0[l] = nnodes;
+            s_tmin[l] = st.tmin;
+          } else {
+#ifndef YK_NO_CLOSEST_RESULTS
+            const unsigned m1 = vconst<0xFFFFFFFFu>(), z = vconst<0u>();
+            hits[r] = yk_hit{(int)m1, __uint_as_float(z), __uint_as_float(z), __uint_as_float(z)};
+#endif
+          }
+        }
+        pending &= ~go;
+      }
+    }
+    const unsigned long long want = GROUP ? 0ull : __ballot(rid < 0 && !exhausted);
     const unsigned long long act = __ballot(rid >= 0);
     if (want != 0ull && (act == 0ull || __popcll(want) >= refill_min)) {
 #ifdef YK_TRAV_STATS
@@ -1361,7 +1440,7 @@ __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned*
     }
 #endif
     if (__ballot(rid >= 0) == 0ull) {
-      if (__ballot(!exhausted) == 0ull) break;
+      if (GROUP ? drained && pending == 0ull : __ballot(!exhausted) == 0ull) break;
       continue;
     }
     bool runaway = false;
@@ -1588,6 +1667,22 @@ k_trace_shadow_split(DScene S, RaySrc src, const unsigned* __restrict__ idx, Ray
   trace_body<false, YK_SHADOW_SEGS, false, false, false, 1, true>(S, src, idx, n, hits, occl, work, ctr, ovf,
                                                                    ovf_depth, refill_min);
 }
+// camera rays: the closest-hit kernel with the group hand-out (trace_body
+// GROUP); refill_min is unused
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
+k_trace_camera(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
+               yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
+               unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
+  trace_body<true, 8, false, false, false, 1, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
+                                                           refill_min);
+}
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
+k_trace_camera_big(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
+                   yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
+                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
+  trace_body<true, 8, false, true, false, 1, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
+                                                          refill_min);
+}
 // trees with a leaf of 2^17 references or more (coop_leaves BIG)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
 k_trace_closest_big(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
@@ -1632,6 +1727,13 @@ k_trace_closest_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, Ra
                       unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
   trace_body<true, 8, false, false, false, YK_SMALL_W>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
                                                        refill_min);
+}
+__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
+k_trace_camera_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
+                     yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
+                     unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
+  trace_body<true, 8, false, false, false, YK_SMALL_W, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf,
+                                                                    ovf_depth, refill_min);
 }
 __global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
 k_trace_shadow_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
@@ -4582,6 +4684,7 @@ enum TraceVariant {
   kClosestBig, kShadowBig,                                            // a leaf of 2^17 references or more
   kShadowUni, kShadowBigUni,                                          // universal-mode scenes
   kClosestSmall, kShadowSmall, kShadowSmallSplit, kShadowUniSmall,  // traversal data in LDS
+  kCamera, kCameraBig, kCameraSmall,                                  // camera rays: group hand-out
   kTraceVariants
 };
 using TraceKernel = void (*)(DScene, RaySrc, const unsigned*, RayCount, yk_hit*, uint8_t*, unsigned long long*,
@@ -4604,6 +4707,9 @@ constexpr TraceInfo kTrace[kTraceVariants] = {
     {k_trace_shadow_small, YK_SMALL_W, true, YK_SMALL_RING},
     {k_trace_shadow_small_split, YK_SMALL_W, true, YK_SMALL_RING},
     {k_trace_shadow_uni_small, YK_SMALL_W, true, YK_SMALL_RING},
+    {k_trace_camera, 1, false, kStackLdsC},
+    {k_trace_camera_big, 1, false, kStackLdsC},
+    {k_trace_camera_small, YK_SMALL_W, true, YK_SMALL_RING},
 };
 
 struct yk_device {
@@ -5118,12 +5224,21 @@ inline RaySrc shadow_src(const Batch& B) {
                 (unsigned)B.kstride};
 }
 
+// Camera rays take the group hand-out kernels (trace_body GROUP);
+// YK_CAMERA_GROUPS=0 (read per render: A/B runs, tests) keeps them on the
+// closest-hit kernels of the bounce rays
+bool camera_groups() {
+  const char* e = std::getenv("YK_CAMERA_GROUPS");
+  return !(e && std::atoi(e) == 0);
+}
+
 // The kernel a trace runs: small scenes (not with big leaves) the LDS-copy
 // kernels, big-leaf trees the BIG ones, universal scenes their own any-hit
 // kernels; split: a render batch's shadow slots in the split form (never
-// universal or big-leaf: shadow_split).
-TraceVariant trace_variant(const yk_device* d, bool closest, bool split) {
+// universal or big-leaf: shadow_split); camera: a render batch's camera rays.
+TraceVariant trace_variant(const yk_device* d, bool closest, bool split, bool camera = false) {
   const bool small = d->small && !d->big_leaves;
+  if (closest && camera) return small ? kCameraSmall : d->big_leaves ? kCameraBig : kCamera;
   if (split) return small ? kShadowSmallSplit : kShadowSplit;
   if (small) return closest ? kClosestSmall : d->S.uni ? kShadowUniSmall : kShadowSmall;
   if (closest) return d->big_leaves ? kClosestBig : kClosest;
@@ -5150,8 +5265,9 @@ void fill_trace_occupancy(yk_device* d, bool dyn_lds) {
 
 template <bool CLOSEST>
 void enqueue_trace(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits,
-                   uint8_t* occ, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0, hipEvent_t ev1) {
-  const TraceVariant v = trace_variant(d, CLOSEST, !CLOSEST && rays.rays == nullptr);
+                   uint8_t* occ, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0, hipEvent_t ev1,
+                   bool camera = false) {
+  const TraceVariant v = trace_variant(d, CLOSEST, !CLOSEST && rays.rays == nullptr, camera);
   const TraceInfo& t = kTrace[v];
   const long long grid = (long long)d->cus * d->per_cu[v];
   const int ovf_depth = std::max(1, stack_depth(d) - t.ring);

@@ -205,6 +205,7 @@ void launch_film_gather(hipStream_t stream, const FilmConst& F, const int* pmap,
 // state is touched, checked parameters are assumed).
 struct FramePlan : TileLists {
   bool pm, cmap, ao, path, merged, split;
+  bool cam_groups;  // camera rays take the group hand-out kernels (camera_groups)
   FilmConst F;
   RenderConst R;
   AOConst AOC;
@@ -291,6 +292,7 @@ const char* build_frame_plan(const yk_device* d, const yk_render_params* p, int3
     return (v > 0 && v <= 240) ? v : 0ll;
   }();
   fp.split = shadow_split(d, p);
+  fp.cam_groups = camera_groups();
   // batches, pipes and every buffer size: plan_batches. YK_BATCH_SAMPLES and
   // YK_PIPES are read on every render (A/B runs, tests)
   yk_batch_plan_in pin{};
@@ -422,13 +424,15 @@ struct BatchCtx {
 unsigned long long* qw(const BatchCtx& c, int isub, int depth) { return c.bw + isub * (c.fp->bounces + 1) + depth; }
 unsigned long long* next_work(BatchCtx& c) { return c.bw + 2ll * c.fp->qwords_per_batch + 128ll * c.launch++; }
 
-void trace(BatchCtx& c, bool closest, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits, uint8_t* occ) {
+// camera: the closest-hit launch over a batch's camera rays, in sample order
+void trace(BatchCtx& c, bool closest, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits, uint8_t* occ,
+           bool camera = false) {
   Pipe& P = *c.P;
   unsigned long long* work = next_work(c);
   const hipEvent_t e0 = P.event(c.evn[c.pi]), e1 = P.event(c.evn[c.pi] + 1);
   c.timed->push_back(Timed{c.pi, c.evn[c.pi], closest});
   c.evn[c.pi] += 2;
-  if (closest) enqueue_trace<true>(c.d, P, rays, idx, n, hits, occ, work, P.words.p, e0, e1);
+  if (closest) enqueue_trace<true>(c.d, P, rays, idx, n, hits, occ, work, P.words.p, e0, e1, camera && c.fp->cam_groups);
   else if (c.B.ts)  // transparent shadows: IntersectTS, filter colour into the slot
     enqueue_trace_ts(c.d, P, rays, idx, n, occ, c.B.s_filt, c.p->shadow_depth, work, P.words.p + kAccWords, e0, e1);
   else enqueue_trace<false>(c.d, P, rays, idx, n, hits, occ, work, P.words.p + kAccWords, e0, e1);
@@ -498,8 +502,10 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   }
   // camera rays of a camera with dead samples: the live ones' queue (k_camera;
   // the shadow queue's buffer, which k_shade_primary fills only afterwards)
+  // (group hand-out: the batch's camera rays as k_camera wrote them, a pixel's
+  // samples consecutive; not the live queue, not the recursion's later nodes)
   if (c.live && node_base == 0) trace(c, true, ray_src(Bc.p_rays), Bc.s_idx, RayCount{c.live, 0, 0}, Bc.p_hits, nullptr);
-  else trace(c, true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr);
+  else trace(c, true, ray_src(Bc.p_rays), nullptr, RayCount{nullptr, 0, n}, Bc.p_hits, nullptr, node_base == 0 && Rc.level == 0);
   // z_channel: the camera samples' depth, before the specular recursion's
   // later generations reuse the hit records
   if (c.zs && node_base == 0) launch(k_depth_samples, grid_for(n), 256, 0, s, Bc.p_rays, Bc.p_hits, c.zs, c.DC, n);
