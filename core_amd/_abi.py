@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("YK_LIB") or os.path.join(_HERE, "libyk.so")  # YK_LIB
 YK_OK = 0
 YK_ERR_ABORTED = 7
 YK_ERR_ARG, YK_ERR_STATE, YK_ERR_HIP, YK_ERR_UNSUPPORTED, YK_ERR_ALLOC, YK_ERR_INTERNAL = 1, 2, 3, 4, 5, 6
-YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT = 0, 1
+YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT, YK_MAT_GLOSSY = 0, 1, 2
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_LIGHT_MESH = 5
 YK_MESH_LIGHT_MAX_TRIS, YK_MESH_LIGHT_MAX_DEPTH = 65536, 29
@@ -41,7 +41,11 @@ class yk_material(C.Structure):
                 ("emit", C.c_float), ("power", C.c_float), ("double_sided", C.c_int32),
                 ("mirror_color", f3), ("specular_reflect", C.c_float), ("transparency", C.c_float),
                 ("translucency", C.c_float), ("transmit_filter", C.c_float), ("fresnel_effect", C.c_int32),
-                ("ior", C.c_double), ("diffuse_brdf", C.c_int32), ("sigma", C.c_double)]
+                ("ior", C.c_double), ("diffuse_brdf", C.c_int32), ("sigma", C.c_double),
+                # appended: the glossy material's parameters
+                ("diffuse_color", f3), ("glossy_reflect", C.c_float), ("exponent", C.c_float),
+                ("as_diffuse", C.c_int32), ("anisotropic", C.c_int32), ("exp_u", C.c_float),
+                ("exp_v", C.c_float)]
 
 
 class yk_light(C.Structure):
@@ -68,7 +72,11 @@ class yk_material_state(C.Structure):
                 ("mirror_color", f3), ("component", C.c_float * 4), ("ncomp", C.c_int32),
                 ("comp_flags", C.c_uint32 * 4), ("comp_index", C.c_int32 * 4), ("transmit_filter", C.c_float),
                 ("has_fresnel", C.c_int32), ("ior_squared", C.c_float), ("oren_nayar", C.c_int32),
-                ("oren_nayar_a", C.c_float), ("oren_nayar_b", C.c_float)]
+                ("oren_nayar_a", C.c_float), ("oren_nayar_b", C.c_float),
+                # appended: glossyMat_t's members
+                ("gloss_color", f3), ("diff_color", f3), ("exponent", C.c_float), ("exp_u", C.c_float),
+                ("exp_v", C.c_float), ("reflectivity", C.c_float), ("m_diffuse", C.c_float),
+                ("as_diffuse", C.c_int32), ("with_diffuse", C.c_int32), ("anisotropic", C.c_int32)]
 
 
 class yk_area_light_state(C.Structure):

@@ -36,7 +36,7 @@ void put(float* d, hv3 v) {
   d[1] = v.y;
   d[2] = v.z;
 }
-constexpr unsigned kSpecular = 0x1u, kDiffuse = 0x4u, kReflect = 0x10u, kTransmit = 0x20u, kFilter = 0x40u,
+constexpr unsigned kSpecular = 0x1u, kGlossy = 0x2u, kDiffuse = 0x4u, kReflect = 0x10u, kTransmit = 0x20u, kFilter = 0x40u,
                    kEmit = 0x80u;  // material.h:49-66
 }  // namespace
 
@@ -47,6 +47,29 @@ yk_material_state material_state(const yk_material& m) {
     o.bsdf_flags = kEmit;
     for (int k = 0; k < 3; ++k) o.color[k] = m.color[k] * m.power;
     o.double_sided = m.double_sided;
+  } else if (m.type == YK_MAT_GLOSSY) {  // glossyMat_t ctor + factory, glossy.cc:65-80,353-389 (no shader nodes)
+    for (int k = 0; k < 3; ++k) {
+      o.gloss_color[k] = m.color[k];
+      o.diff_color[k] = m.diffuse_color[k];
+    }
+    o.exponent = m.exponent;
+    o.reflectivity = m.glossy_reflect;
+    o.m_diffuse = m.diffuse_reflect;
+    o.as_diffuse = m.as_diffuse ? 1 : 0;
+    if (m.diffuse_reflect > 0.f) {
+      o.bsdf_flags = kDiffuse | kReflect;
+      o.with_diffuse = 1;
+    }
+    o.bsdf_flags |= o.as_diffuse ? (kDiffuse | kReflect) : (kGlossy | kReflect);
+    o.anisotropic = m.anisotropic ? 1 : 0;
+    o.exp_u = m.exp_u;
+    o.exp_v = m.exp_v;
+    if (m.diffuse_brdf == YK_BRDF_OREN_NAYAR) {  // glossyMat_t::initOrenNayar(sigma), glossy.cc:97-103
+      const double sigma2 = m.sigma * m.sigma;
+      o.oren_nayar = 1;
+      o.oren_nayar_a = (float)(1.0 - 0.5 * (sigma2 / (sigma2 + 0.33)));
+      o.oren_nayar_b = (float)(0.45 * sigma2 / (sigma2 + 0.09));
+    }
   } else {  // shinyDiffuseMat_t ctor + factory + config(), shinydiffuse.cc:9-80,474-562
     if (m.emit > 0.f) o.bsdf_flags |= kEmit;
     for (int k = 0; k < 3; ++k) {

@@ -35,6 +35,7 @@
 #include "../../include/yk_test_hooks_camera.h"
 #include "../../include/yk_test_hooks_film.h"
 #include "../../include/yk_test_hooks_depth.h"
+#include "../../include/yk_test_hooks_material.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"
@@ -57,19 +58,34 @@ struct DMat {
   float col[3];       // diffuse colour (shinydiffuse) / lightCol = col*power (light_mat)
   float emit_col[3];  // mEmitColor = emit * color (shinydiffuse.cc:12)
   int double_sided;
-  // shinyDiffuseMat_t after config() (shinydiffuse.cc:27-80)
-  float comp[4];      // getComponents: mirror, transparency, translucency, diffuse
-  float mirror[3];    // mMirrorColor
-  int ncomp;          // nBSDF
-  unsigned cflags[4]; // cFlags
-  int cindex[4];      // cIndex
-  float tfilter;      // mTransmitFilterStrength
-  int fresnel;        // mHasFresnelEffect
-  float ior2;         // mIOR_Squared
-  int translucent;    // mIsTranslucent
-  int on;             // mUseOrenNayar (shinydiffuse.cc:170-176)
-  float on_a, on_b;   // mOrenNayar_A / mOrenNayar_B
+  // The record keeps its size and the shinydiffuse members their offsets (the
+  // shading kernels hold all kMaxMats records in LDS): a glossy material's
+  // members lie over the shinydiffuse ones, which it does not have.
+  union {
+    struct {  // shinyDiffuseMat_t after config() (shinydiffuse.cc:27-80)
+      float comp[4];      // getComponents: mirror, transparency, translucency, diffuse
+      float mirror[3];    // mMirrorColor
+      int ncomp;          // nBSDF
+      unsigned cflags[4]; // cFlags
+      int cindex[4];      // cIndex
+      float tfilter;      // mTransmitFilterStrength
+      int fresnel;        // mHasFresnelEffect
+      float ior2;         // mIOR_Squared
+      int translucent;    // mIsTranslucent
+    };
+    struct {  // glossyMat_t (glossy.cc:56-62) with as_diffuse; col above is gloss_color
+      float diff[3];      // diff_color
+      float exponent, exp_u, exp_v;
+      float m_glossy;     // MDat_t::mGlossy = reflectivity (no shader node)
+      float m_diffuse;    // mDiffuse
+      float p_diffuse;    // MDat_t::pDiffuse (glossy.cc:94), constant without nodes
+      int with_diffuse, anisotropic;
+    } gl;
+  };
+  int on;             // mUseOrenNayar (shinydiffuse.cc:170-176) / glossyMat_t::orenNayar
+  float on_a, on_b;   // mOrenNayar_A / mOrenNayar_B, orenA / orenB
 };
+static_assert(sizeof(DMat) == 32 * sizeof(int), "DMat: the shading kernels' LDS copy is sized by it");
 
 struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-49)
   float corner[3], toX[3], toY[3], fnormal[3], c2[3], c3[3], c4[3], color[3];
@@ -1838,13 +1854,267 @@ __device__ __forceinline__ float oren_nayar(const DMat& M, v3 wi, v3 wo, v3 N) {
   return M.on_a + ((M.on_b * maxcos_f) * sin_alpha) * tan_beta;
 }
 
+// ---- glossy (glossyMat_t, glossy.cc; microfacet.h; mathOptimizations.h) ----
+// In source order (no reference output holds a glossy material, so nothing
+// pins a compiled form); std::min / std::max as the ternaries <algorithm>
+// defines, so a NaN operand falls through as it does there.
+
+// fLog2 / fExp2 / fPow (FAST_MATH), mathOptimizations.h:83-125,200-207: integer
+// arithmetic on the float's bits, so zero and negative bases have values too
+// (the sign bit is masked off, zero reads as exponent -127). POLYLOG's fourth
+// constant is a double literal: the polynomial's outer three steps run in
+// double. A NaN exponent is outside what the reference defines ((int) of it).
+__device__ __forceinline__ float fexp2_ref(float x) {
+  x = (129.00000f < x) ? 129.00000f : x;    // std::min(x, f_HI)
+  x = (x < -126.99999f) ? -126.99999f : x;  // std::max(x, f_LOW)
+  const int ipart = (int)(x - 0.5f);
+  const float f = x - (float)ipart;
+  const float expipart = __int_as_float((int)((unsigned)(ipart + 127) << 23));
+  const float poly =
+      f * (f * (f * (f * (f * 1.8775767e-3f + 8.9893397e-3f) + 5.5826318e-2f) + 2.4015361e-1f) + 6.9315308e-1f) +
+      9.9999994e-1f;
+  return expipart * poly;
+}
+__device__ __forceinline__ float flog2_ref(float x) {
+  const int i = __float_as_int(x);
+  const float e = (float)(((i & 0x7F800000) >> 23) - 127);
+  const float m = __int_as_float((i & 0x7FFFFF) | 0x3F800000);
+  const float p2 = m * (m * -3.4436006e-2f + 3.1821337e-1f) + -1.2315303f;
+  const double p5 = (double)m * ((double)m * ((double)(m * p2) + 2.5988452) + (double)-3.3241990f) + (double)3.1157899f;
+  return (float)p5 * (m - 1.0f) + e;
+}
+__device__ __forceinline__ float fpow_ref(float a, float b) { return fexp2_ref(flog2_ref(a) * b); }
+
+// pdfDivisor / ASDivisor, microfacet.h:35-43: 8.f * M_PI is a double
+__device__ __forceinline__ float gl_pdf_divisor(float c) { return (float)(8.0 * YK_PI_D * (double)(c * 0.99f + 0.04f)); }
+__device__ __forceinline__ float gl_as_divisor(float cos1, float cosI, float cosO) {
+  const float mx = (cosI < cosO) ? cosO : cosI;  // std::max(cosI, cosO)
+  return (float)(8.0 * YK_PI_D * (double)((cos1 * mx) * 0.99f + 0.04f));
+}
+// SchlickFresnel, microfacet.h:195-200
+__device__ __forceinline__ float gl_schlick(float costheta, float R) {
+  const float c1 = 1.f - costheta;
+  const float c2 = c1 * c1;
+  return R + ((1.f - R) * c1 * c2 * c2);
+}
+// Blinn_D, AS_Aniso_D, microfacet.h:60-65,96-99
+__device__ __forceinline__ float gl_blinn_d(float cos_h, float e) { return (e + 1.f) * fpow_ref(cos_h, e); }
+__device__ __forceinline__ float gl_aniso_d(v3 h, float e_u, float e_v) {
+  if (h.z <= 0.f) return 0.f;
+  const float exponent = (e_u * h.x * h.x + e_v * h.y * h.y) / (1.00001f - h.z * h.z);
+  return sqrtf((e_u + 1.f) * (e_v + 1.f)) * fpow_ref((0.f < h.z) ? h.z : 0.f, exponent);
+}
+// the lobe's D for half vector H: Blinn over H.N or Ashikhmin-Shirley over H in the (NU, NV, N) frame
+__device__ __forceinline__ float gl_lobe_d(const DMat& M, const SurfPt& sp, v3 H, float cos_N_H) {
+  if (M.gl.anisotropic) return gl_aniso_d(V3(vdot(H, sp.NU), vdot(H, sp.NV), cos_N_H), M.gl.exp_u, M.gl.exp_v);
+  return gl_blinn_d(cos_N_H, M.gl.exponent);
+}
+// sample_quadrant_aniso / AS_Aniso_Sample, microfacet.h:45-58,72-94. atan and
+// tanf are the device library's atanf and tanf (unpinned, like the angular
+// camera's atan2f); M_PI_2 * s1 is a double product.
+__device__ __forceinline__ v3 gl_sample_quadrant(float s1, float s2, float e_u, float e_v) {
+  const float phi = atanf(sqrtf((e_u + 1.f) / (e_v + 1.f)) * tanf((float)(1.57079632679489661923 * (double)s1)));
+  const float cosPhi = fcos_ref(phi), sinPhi = fsin_ref(phi);
+  const float cosPhi2 = cosPhi * cosPhi;
+  const float sinPhi2 = 1.f - cosPhi2;
+  const float cosTheta = fpow_ref(1.f - s2, 1.f / (e_u * cosPhi2 + e_v * sinPhi2 + 1.f));
+  const float sinTheta = sqrtf(1.f - cosTheta * cosTheta);
+  return V3(sinTheta * cosPhi, sinTheta * sinPhi, cosTheta);
+}
+__device__ __forceinline__ v3 gl_aniso_sample(float s1, float s2, float e_u, float e_v) {
+  v3 H;
+  if (s1 < 0.25f) {
+    H = gl_sample_quadrant(4.f * s1, s2, e_u, e_v);
+  } else if (s1 < 0.5f) {
+    H = gl_sample_quadrant(1.f - 4.f * (0.5f - s1), s2, e_u, e_v);
+    H.x = -H.x;
+  } else if (s1 < 0.75f) {
+    H = gl_sample_quadrant(4.f * (s1 - 0.5f), s2, e_u, e_v);
+    H.x = -H.x;
+    H.y = -H.y;
+  } else {
+    H = gl_sample_quadrant(1.f - 4.f * (1.f - s1), s2, e_u, e_v);
+    H.y = -H.y;
+  }
+  return H;
+}
+// Blinn_Sample, microfacet.h:106-113: phi = s1 * M_2PI is a double product
+__device__ __forceinline__ v3 gl_blinn_sample(float s1, float s2, float exponent) {
+  const float cosTheta = fpow_ref(1.f - s2, 1.f / (exponent + 1.f));
+  const float sinTheta = sqrtf(1.f - cosTheta * cosTheta);
+  const float phi = (float)((double)s1 * YK_2PI_D);
+  return V3(sinTheta * fcos_ref(phi), sinTheta * fsin_ref(phi), cosTheta);
+}
+// diffuseReflect, microfacet.h:202-212: the product runs in double from
+// DIFFUSE_RATIO on and is rounded to float where it meets the colour
+__device__ __forceinline__ c3 gl_diffuse_reflect(float wiN, float woN, float mGlossy, float mDiffuse, c3 base) {
+  float f_wi = 1.f - (0.5f * wiN);
+  float temp = f_wi * f_wi;
+  f_wi = temp * temp * f_wi;
+  float f_wo = 1.f - (0.5f * woN);
+  temp = f_wo * f_wo;
+  f_wo = temp * temp * f_wo;
+  const float k = (float)(0.387507688 * (double)mDiffuse * (double)(1.f - mGlossy) * (double)(1.f - f_wi) *
+                          (double)(1.f - f_wo));
+  return cscale(k, base);
+}
+// glossyMat_t::OrenNayar, glossy.cc:105-132 (its clamps are not shinydiffuse's)
+__device__ __forceinline__ float gl_oren_nayar(const DMat& M, v3 wi, v3 wo, v3 N) {
+  const float di = vdot(N, wi), dO = vdot(N, wo);
+  const float mi = (di < 1.f) ? di : 1.f, mo = (dO < 1.f) ? dO : 1.f;
+  const float cos_ti = (-1.f < mi) ? mi : -1.f, cos_to = (-1.f < mo) ? mo : -1.f;
+  float maxcos_f = 0.f;
+  if (cos_ti < 0.9999f && cos_to < 0.9999f) {
+    const v3 v1 = vnormalize(vsub(wi, vmul(cos_ti, N)));
+    const v3 v2 = vnormalize(vsub(wo, vmul(cos_to, N)));
+    const float d = vdot(v1, v2);
+    maxcos_f = (0.f < d) ? d : 0.f;
+  }
+  float sin_alpha, tan_beta;
+  if (cos_to >= cos_ti) {
+    sin_alpha = sqrtf(1.f - cos_ti * cos_ti);
+    tan_beta = sqrtf(1.f - cos_to * cos_to) / ((cos_to == 0.f) ? 1e-8f : cos_to);
+  } else {
+    sin_alpha = sqrtf(1.f - cos_to * cos_to);
+    tan_beta = sqrtf(1.f - cos_ti * cos_ti) / ((cos_ti == 0.f) ? 1e-8f : cos_ti);
+  }
+  return M.on_a + M.on_b * maxcos_f * sin_alpha * tan_beta;
+}
+
+// glossyMat_t::eval, glossy.cc:134-173 (as_diffuse). The diffuse base is
+// mDiffuse * (1 - mGlossy) * diff_color * OrenNayar here; sample() uses
+// diffuseReflect instead.
+__device__ __forceinline__ c3 glossy_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wi, unsigned bsdfs) {
+  if (!(bsdfs & BSDF_DIFFUSE) || (vdot(sp.Ng, wi) * vdot(sp.Ng, wo)) < 0.f) return C3(0.f, 0.f, 0.f);
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  const float wiN = fabsf(vdot(wi, N)), woN = fabsf(vdot(wo, N));
+  const v3 H = vnormalize(vadd(wo, wi));
+  const float d = vdot(wi, H);
+  const float cos_wi_H = (0.f < d) ? d : 0.f;
+  const float glossy =
+      gl_lobe_d(M, sp, H, vdot(H, N)) * gl_schlick(cos_wi_H, M.gl.m_glossy) / gl_as_divisor(cos_wi_H, woN, wiN);
+  c3 col = cscale(glossy, C3(M.col[0], M.col[1], M.col[2]));
+  if (M.gl.with_diffuse) {
+    const c3 dc = cscale(M.gl.m_diffuse * (1.f - M.gl.m_glossy), C3(M.gl.diff[0], M.gl.diff[1], M.gl.diff[2]));
+    col = cadd(col, cscale(M.on ? gl_oren_nayar(M, wi, wo, N) : 1.f, dc));
+  }
+  return col;
+}
+
+// glossyMat_t::sample, glossy.cc:176-305 (as_diffuse). ok = false where the
+// reference returns before it writes W: black, W untouched -- but wi, pdf and,
+// in the diffuse half, sampledFlags are already written by then, as there.
+__device__ __forceinline__ c3 glossy_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1, float s2,
+                                            unsigned flags, float& pdf, float& W, bool& ok, unsigned& sflags) {
+  const float cos_Ng_wo = vdot(sp.Ng, wo);
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  pdf = 0.f;
+  float wiN = 0.f;
+  const float woN = fabsf(vdot(wo, N));
+  c3 scolor = C3(0.f, 0.f, 0.f);
+  const float pD = M.gl.p_diffuse, mG = M.gl.m_glossy;
+  const bool use_glossy = (flags & BSDF_DIFFUSE) != 0;
+  const bool use_diffuse = M.gl.with_diffuse && (flags & BSDF_DIFFUSE);
+  const c3 gcol = C3(M.col[0], M.col[1], M.col[2]), dcol = C3(M.gl.diff[0], M.gl.diff[1], M.gl.diff[2]);
+  float glossy = 0.f;
+  if (use_diffuse) {
+    const float s_pDiffuse = use_glossy ? pD : 1.f;
+    if (s1 < s_pDiffuse) {
+      s1 /= s_pDiffuse;
+      wi = sample_cos_hemisphere(N, sp.NU, sp.NV, s1, s2);
+      if (vdot(sp.Ng, wi) * cos_Ng_wo < 0.f) {
+        ok = false;
+        return scolor;
+      }
+      wiN = fabsf(vdot(wi, N));
+      pdf = wiN;
+      if (use_glossy) {
+        const v3 H = vnormalize(vadd(wi, wo));
+        const float cos_wo_H = vdot(wo, H), cos_wi_H = fabsf(vdot(wi, H)), cos_N_H = vdot(N, H);
+        const float D = gl_lobe_d(M, sp, H, cos_N_H);
+        pdf = pdf * pD + (D / gl_pdf_divisor(cos_wo_H)) * (1.f - pD);
+        glossy = D * gl_schlick(cos_wi_H, mG) / gl_as_divisor(cos_wi_H, woN, wiN);
+      }
+      sflags = BSDF_DIFFUSE | BSDF_REFLECT;
+      if (!(flags & BSDF_REFLECT)) {
+        ok = false;
+        return C3(0.f, 0.f, 0.f);
+      }
+      scolor = cscale(glossy, gcol);
+      scolor = cadd(scolor, cscale(M.on ? gl_oren_nayar(M, wi, wo, N) : 1.f, gl_diffuse_reflect(wiN, woN, mG, M.gl.m_diffuse, dcol)));
+      W = wiN / (pdf * 0.99f + 0.01f);
+      return scolor;
+    }
+    s1 -= pD;
+    s1 /= (1.f - pD);
+  }
+  if (use_glossy) {
+    const v3 Hs = M.gl.anisotropic ? gl_aniso_sample(s1, s2, M.gl.exp_u, M.gl.exp_v) : gl_blinn_sample(s1, s2, M.gl.exponent);
+    v3 H = vadd(vadd(vmul(Hs.x, sp.NU), vmul(Hs.y, sp.NV)), vmul(Hs.z, N));
+    float cos_wo_H = vdot(wo, H);
+    if (cos_wo_H < 0.f) {  // H.reflect(N), vector3d.h:288-295
+      const float vn = 2.0f * vdot(H, N);
+      H = V3(vn * N.x - H.x, vn * N.y - H.y, vn * N.z - H.z);
+      cos_wo_H = vdot(wo, H);
+    }
+    {  // reflect_dir(H, wo), vector3d.h:297-302
+      const float vn = vdot(wo, H);
+      if (vn < 0.f) {
+        wi = vneg(wo);
+      } else {
+        const float v2 = 2.f * vn;
+        wi = V3(v2 * H.x - wo.x, v2 * H.y - wo.y, v2 * H.z - wo.z);
+      }
+    }
+    if (cos_Ng_wo * vdot(sp.Ng, wi) < 0.f) {
+      ok = false;
+      return C3(0.f, 0.f, 0.f);
+    }
+    wiN = fabsf(vdot(wi, N));
+    // the anisotropic branch evaluates D on the sampled Hs, the Blinn one on H.N after the reflection
+    const float D = M.gl.anisotropic ? gl_aniso_d(Hs, M.gl.exp_u, M.gl.exp_v) : gl_blinn_d(vdot(H, N), M.gl.exponent);
+    pdf = D / gl_pdf_divisor(cos_wo_H);
+    glossy = D * gl_schlick(cos_wo_H, mG) / gl_as_divisor(cos_wo_H, woN, wiN);
+    scolor = cscale(glossy, gcol);
+    sflags = BSDF_DIFFUSE | BSDF_REFLECT;
+  }
+  if (use_diffuse) {
+    pdf = wiN * pD + pdf * (1.f - pD);
+    scolor = cadd(scolor, cscale(M.on ? gl_oren_nayar(M, wi, wo, N) : 1.f, gl_diffuse_reflect(wiN, woN, mG, M.gl.m_diffuse, dcol)));
+  }
+  W = wiN / (pdf * 0.99f + 0.01f);
+  return scolor;
+}
+
+// glossyMat_t::pdf, glossy.cc:307-351 (as_diffuse)
+__device__ __forceinline__ float glossy_pdf(const DMat& M, const SurfPt& sp, v3 wo, v3 wi, unsigned flags) {
+  if (vdot(sp.Ng, wo) * vdot(sp.Ng, wi) < 0.f) return 0.f;
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  const bool use_glossy = (flags & BSDF_DIFFUSE) != 0;
+  const bool use_diffuse = M.gl.with_diffuse && (flags & BSDF_DIFFUSE);
+  float pdf = 0.f;
+  if (use_diffuse) pdf = fabsf(vdot(wi, N));
+  if (use_glossy) {
+    const v3 H = vnormalize(vadd(wi, wo));
+    const float lobe = gl_lobe_d(M, sp, H, vdot(N, H)) / gl_pdf_divisor(vdot(wo, H));
+    pdf = use_diffuse ? pdf * M.gl.p_diffuse + lobe * (1.f - M.gl.p_diffuse) : lobe;
+  }
+  return pdf;
+}
+
 // shinyDiffuseMat_t::eval, shinydiffuse.cc:223-249 (compiled: cos_Ng_wl as
 // (y + z) + x; mD = ((1-c2)*c3)*mT), then mD *= OrenNayar(wo, wl, N) (:247).
 // ON = false: the scene has no Oren-Nayar material (the diffuse-only
 // instantiation's scenes), so the factor's code is not compiled in.
-template <bool ON = true>
+// GL = true: the scene holds a glossy material; only then is glossy's code
+// compiled in (mat_sample and mat_pdf likewise), so every other scene runs
+// the kernels it ran before. bsdfs is BSDF_ALL at every call site.
+template <bool ON = true, bool GL = false>
 __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wl) {
   if (M.type == YK_MAT_LIGHT) return C3(0.f, 0.f, 0.f);
+  if constexpr (GL) {
+    if (M.type == YK_MAT_GLOSSY) return glossy_eval(M, sp, wo, wl, BSDF_ALL);
+  }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const float cos_Ng_wl = (sp.Ng.y * wl.y + sp.Ng.z * wl.z) + sp.Ng.x * wl.x;
   const v3 N = (cos_Ng_wo < 0.f) ? vneg(sp.N) : sp.N;
@@ -1870,15 +2140,19 @@ __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v
 // same float operations on the same values -- sum = 0 + w, the normalisation
 // by 1/sum, s1 / wp -- without the loop's per-lane arrays (the shading
 // kernels' registers).
-template <bool DIFF = false>
+template <bool DIFF = false, bool GL = false>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok, unsigned& sflags) {
+  static_assert(!(DIFF && GL), "a scene with a glossy material is never diffuse-only");
   ok = true;
   sflags = 0u;
   if (M.type == YK_MAT_LIGHT) {
     pdf = 0.f;
     W = 0.f;
     return C3(0.f, 0.f, 0.f);
+  }
+  if constexpr (GL) {
+    if (M.type == YK_MAT_GLOSSY) return glossy_sample(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sflags);
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const v3 N = (cos_Ng_wo < 0.f) ? vneg(sp.N) : sp.N;
@@ -1979,19 +2253,24 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
   W = fabsf(vdot(w, sp.N)) / (pdf * 0.99f + 0.01f);
   return sc;
 }
-template <bool DIFF = false>
+template <bool DIFF = false, bool GL = false>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok) {
   unsigned sf;
-  return mat_sample<DIFF>(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sf);
+  return mat_sample<DIFF, GL>(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sf);
 }
 
 // shinyDiffuseMat_t::pdf, shinydiffuse.cc:338-377: every component sharing a
 // bit with bsdfs adds its width to the sum; only diffuse ones add pdf.
 // Called with bsdfs = GLOSSY|DIFFUSE|DISPERSIVE|REFLECT|TRANSMIT, which
 // overlaps every shinydiffuse component.
+template <bool GL = false>
 __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo, v3 wi) {
   if (M.type == YK_MAT_LIGHT) return 0.f;
+  if constexpr (GL) {
+    if (M.type == YK_MAT_GLOSSY)
+      return glossy_pdf(M, sp, wo, wi, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
+  }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const v3 N = (cos_Ng_wo < 0.f) ? vneg(sp.N) : sp.N;
   const float Kr = mat_fresnel(M, wo, N);
@@ -2958,7 +3237,7 @@ __device__ __forceinline__ bool light_sampled(const DLight& L) {
   return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.type == YK_LIGHT_MESH || L.soft != 0;
 }
 
-template <bool DIFF, int KIND>
+template <bool DIFF, int KIND, bool GL = false>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
                                            unsigned loffs, unsigned long long& traced,
@@ -2971,7 +3250,7 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
 // XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light) or
 // kXLMesh (it holds a mesh light; ml = DScene::ml): see shade_primary_fn
 constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2;
-template <bool DIFF = false, int XL = kXLNone>
+template <bool DIFF = false, int XL = kXLNone, bool GL = false>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
                                          unsigned long long& traced, const DMat* mats = c_mats,
@@ -2982,13 +3261,13 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
   // the light's kind is the same for every lane: one scalar branch per light,
   // outside the sample loops
   if (L.type == YK_LIGHT_AREA)
-    return gen_sampled<DIFF, YK_LIGHT_AREA>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+    return gen_sampled<DIFF, YK_LIGHT_AREA, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
   if (XL == kXLMesh && L.type == YK_LIGHT_MESH)
-    return gen_sampled<DIFF, YK_LIGHT_MESH>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced, ml + L.mesh);
+    return gen_sampled<DIFF, YK_LIGHT_MESH, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced, ml + L.mesh);
   if (XL && L.type == YK_LIGHT_SPHERE)
-    return gen_sampled<DIFF, YK_LIGHT_SPHERE>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+    return gen_sampled<DIFF, YK_LIGHT_SPHERE, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
   if (XL && L.soft)
-    return gen_sampled<DIFF, YK_LIGHT_SPOT>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+    return gen_sampled<DIFF, YK_LIGHT_SPOT, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
   {  // Dirac branch, mcintegrator.cc:85-100: one shadow ray
     const long long slot = slot_of(B, c, k0);
     v3 ldir;
@@ -2999,7 +3278,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
       return 0;
     }
     const int nq = emit_shadow<false>(B, slot, sp.P, ldir, ltmax, k0, traced);
-    const c3 surf = mat_eval<!DIFF>(M, sp, wo, ldir);
+    const c3 surf = mat_eval<!DIFF, GL>(M, sp, wo, ldir);
     const float f = fabsf(vdot(sp.N, ldir));
     if (B.ts) {  // lcol *= scol first (mcintegrator.cc:94): keep the parts
       put_slot(B, slot, SL_TRACED | SL_ADDS, surf);
@@ -3022,7 +3301,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 // transparent shadows, which filter the colour first). A sphere light's
 // canIntersect() is false (spherelight.cc:49): no MIS weight on its light
 // samples and no BSDF half, so it owns `samples` slots, not 2 * samples.
-template <bool DIFF, int KIND>
+template <bool DIFF, int KIND, bool GL>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
                                            unsigned loffs, unsigned long long& traced, const DMeshLight* ml) {
@@ -3056,8 +3335,8 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
       put_slot(B, slot, SL_TRACED, black);
       continue;
     }
-    const c3 surf = mat_eval<!DIFF>(M, sp, wo, ldir);
-    const float mPdf = CAN_INTERSECT ? mat_pdf(M, sp, wo, ldir) : 0.f;
+    const c3 surf = mat_eval<!DIFF, GL>(M, sp, wo, ldir);
+    const float mPdf = CAN_INTERSECT ? mat_pdf<GL>(M, sp, wo, ldir) : 0.f;
     // compiled form: ((surf*lcol) * (|N.l| * (1/pdf))) [* w]
     const float k = fabsf(vdot(sp.N, ldir)) * (1.0f / lpdf);
     float w = 1.f;
@@ -3085,7 +3364,7 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
     float W = 0.f, spdf = 0.f;
     bool ok;
     v3 bdir = V3(0.f, 0.f, 0.f);
-    const c3 surf = mat_sample<DIFF>(M, sp, wo, bdir, s1, s2,
+    const c3 surf = mat_sample<DIFF, GL>(M, sp, wo, bdir, s1, s2,
                                      BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT, spdf,
                                      W, ok);
     float bt, lightPdf, cv = 1.f;
@@ -3142,7 +3421,7 @@ constexpr unsigned kAOFlags = BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_REFLECT;
 // returns early (no component matches, or their widths sum below 1e-5) leaves
 // W = 0 and the previous direction: its term is +0 whatever the ray meets,
 // and the slot traces nothing.
-template <bool DIFF>
+template <bool DIFF, bool GL = false>
 __device__ __forceinline__ int gen_ao(const Batch& B, long long c, const AOConst& A, const DMat& M, const SurfPt& sp,
                                       v3 wo, unsigned pixelSample, unsigned soffs, unsigned long long& traced) {
   const c3 black = C3(0.f, 0.f, 0.f);
@@ -3158,7 +3437,7 @@ __device__ __forceinline__ int gen_ao(const Batch& B, long long c, const AOConst
     float W = 0.f, pdf = 0.f;
     bool ok;
     v3 dir = V3(0.f, 0.f, 0.f);
-    const c3 surf = mat_sample<DIFF>(M, sp, wo, dir, s1, s2, kAOFlags, pdf, W, ok);
+    const c3 surf = mat_sample<DIFF, GL>(M, sp, wo, dir, s1, s2, kAOFlags, pdf, W, ok);
     if (!ok) {
       put_slot(B, slot, 0, black);
       continue;
@@ -3191,7 +3470,7 @@ __device__ __forceinline__ void flush_shadow(const Batch& B, long long c, int ke
 
 // First segment of sub-path isub from a diffuse camera-ray hit: sample the
 // primary BSDF (pathtracer.cc:169-187). Returns the segment's ray.
-template <bool DIFF = false>
+template <bool DIFF = false, bool GL = false>
 __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const RenderConst& R, long long c,
                                                      const SurfPt& sp, const DMat& M, v3 dir, int isub) {
   const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
@@ -3201,7 +3480,7 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
   float pdf, W = B.wlast[c];
   bool ok;
   v3 pdir = V3(0.f, 0.f, 0.f);
-  c3 scol = mat_sample<DIFF>(M, sp, vneg(dir), pdir, s1, s2, BSDF_DIFFUSE | BSDF_REFLECT | BSDF_TRANSMIT, pdf, W, ok);
+  c3 scol = mat_sample<DIFF, GL>(M, sp, vneg(dir), pdir, s1, s2, BSDF_DIFFUSE | BSDF_REFLECT | BSDF_TRANSMIT, pdf, W, ok);
   B.wlast[c] = W;
   scol = cscale(W, scol);
   B.thr[3 * c] = scol.r;
@@ -3224,7 +3503,8 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // (spills of 124-200 B per lane) predates their register diet.
 // AO: direct lighting with ambient occlusion (gen_ao) -- an instantiation of
 // its own, so the others carry none of its code; A is read by it alone.
-template <bool DIFF, int XL, bool AO>
+// GL: the scene holds a glossy material (mat_eval); DIFF is false then.
+template <bool DIFF, int XL, bool AO, bool GL = false>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
                                                        unsigned long long* __restrict__ qword, AOConst A) {
   // The material records in LDS: per-lane reads of constant memory (the
@@ -3280,19 +3560,19 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
         const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
         int k0 = 0;
         for (int l = 0; l < R.nlights; ++l) {
-          nr += gen_light<DIFF, XL>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats, S.ml);
+          nr += gen_light<DIFF, XL, GL>(B, c, k0, l, sp, wo, s, B.soffs[c], (unsigned)l, traced, s_mats, S.ml);
           k0 += c_lights[l].nslots;
         }
         kend = k0;
         if constexpr (AO) {
-          nr += gen_ao<DIFF>(B, c, A, M, sp, wo, s, B.soffs[c], traced);
+          nr += gen_ao<DIFF, GL>(B, c, A, M, sp, wo, s, B.soffs[c], traced);
           kend = A.k0 + A.n;
           if (M.flags & BSDF_EMIT) ph |= PH_AOEMIT;
         }
         if (nr) put_org(B, c, sp.P);
         if (R.integrator == YK_INTEGRATOR_PATH) {
           B.wlast[c] = 0.f;
-          seg = path_first_segment<DIFF>(B, R, c, sp, M, dir, 0);
+          seg = path_first_segment<DIFF, GL>(B, R, c, sp, M, dir, 0);
           emit = true;
           if (R.spec) {  // state.includeLights = false before the first segment's intersect
             B.incl[c] = 0;
@@ -3454,7 +3734,7 @@ __global__ void __launch_bounds__(256) k_resolve_ao(DScene S, Batch B, RenderCon
 
 // First segment of sub-paths isub >= 1 (sub-path 0 is fused into
 // k_shade_primary).
-template <bool DIFF>
+template <bool DIFF, bool GL = false>
 __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch B, RenderConst R, long long nc, int isub,
                                                     unsigned long long* __restrict__ qword) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3466,7 +3746,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
     const yk_ray pr = B.p_rays[c];
     const v3 from = V3(pr.from[0], pr.from[1], pr.from[2]), dir = V3(pr.dir[0], pr.dir[1], pr.dir[2]);
     const SurfPt sp = make_surface(S, from, dir, h);
-    r = path_first_segment<DIFF>(B, R, c, sp, c_mats[sp.mat], dir, isub);
+    r = path_first_segment<DIFF, GL>(B, R, c, sp, c_mats[sp.mat], dir, isub);
     emit = true;
     if (R.spec) {
       B.incl[c] = 0;
@@ -3485,7 +3765,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
 // (pathtracer.cc:189-298): estimateOneDirectLight shadow rays, emission,
 // and the BSDF sample of the next segment. One thread per live path (entry
 // qi of the input bounce queue, owned by camera sample c).
-template <bool DIFF, int XL>
+template <bool DIFF, int XL, bool GL = false>
 __global__ void __launch_bounds__(bounce_block(DIFF))
 __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES))) k_shade_bounce(DScene S, Batch B, RenderConst R,
                                                       const unsigned long long* __restrict__ qin_word, int depth,
@@ -3545,8 +3825,8 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
         // compiler reads its record with scalar loads instead of per-lane
         // vector loads (which go through the texture path that limits this
         // kernel, PMC TD busy 0.9)
-        if (R.nlights == 1) nr = gen_light<DIFF, XL>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced, c_mats, S.ml);
-        else nr = gen_light<DIFF, XL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced, c_mats, S.ml);
+        if (R.nlights == 1) nr = gen_light<DIFF, XL, GL>(B, c, 0, 0, sp, pwo, s, B.soffs[c], 0u, traced, c_mats, S.ml);
+        else nr = gen_light<DIFF, XL, GL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced, c_mats, S.ml);
         kend = c_lights[lnum].nslots;
         if (nr) put_org(B, c, sp.P);
         if (R.nlights > 1) B.lsel[c] = lnum;  // one light: the resolve knows it is light 0
@@ -3579,7 +3859,7 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
         bool ok;
         v3 ndir = dir;  // pRay.dir keeps the previous direction if sample() returns early
         unsigned sfl;
-        c3 sc = mat_sample<DIFF>(M, sp, pwo, ndir, s1, s2, BSDF_ALL, pdf, W, ok, sfl);
+        c3 sc = mat_sample<DIFF, GL>(M, sp, pwo, ndir, s1, s2, BSDF_ALL, pdf, W, ok, sfl);
         B.wlast[c] = W;
         sc = cscale(W, sc);
         if (!cblack(sc)) {
@@ -3620,7 +3900,14 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
 // sphere code: meshLight_t::intersect walks the light's kd-tree per BSDF-half
 // sample with a per-lane stack in scratch memory (MeshStack), which no other
 // scene pays for.
-inline auto shade_primary_fn(bool diff, int xl, bool ao) {
+// A glossy material (GL) adds general-material instantiations of its own in
+// the same way, one per XL x AO: glossy's lobe code reaches no other scene.
+inline auto shade_primary_fn(bool diff, int xl, bool ao, bool gl) {
+  if (gl) {
+    if (xl == kXLMesh) return ao ? k_shade_primary<false, kXLMesh, true, true> : k_shade_primary<false, kXLMesh, false, true>;
+    if (xl) return ao ? k_shade_primary<false, kXLSpotSphere, true, true> : k_shade_primary<false, kXLSpotSphere, false, true>;
+    return ao ? k_shade_primary<false, kXLNone, true, true> : k_shade_primary<false, kXLNone, false, true>;
+  }
   if (xl == kXLMesh) {
     if (ao) return diff ? k_shade_primary<true, kXLMesh, true> : k_shade_primary<false, kXLMesh, true>;
     return diff ? k_shade_primary<true, kXLMesh, false> : k_shade_primary<false, kXLMesh, false>;
@@ -3631,7 +3918,10 @@ inline auto shade_primary_fn(bool diff, int xl, bool ao) {
   return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, false> : k_shade_primary<false, kXLSpotSphere, false>)
             : (diff ? k_shade_primary<true, kXLNone, false> : k_shade_primary<false, kXLNone, false>);
 }
-inline auto shade_bounce_fn(bool diff, int xl) {
+inline auto shade_bounce_fn(bool diff, int xl, bool gl) {
+  if (gl)
+    return xl == kXLMesh ? k_shade_bounce<false, kXLMesh, true>
+                         : (xl ? k_shade_bounce<false, kXLSpotSphere, true> : k_shade_bounce<false, kXLNone, true>);
   if (xl == kXLMesh) return diff ? k_shade_bounce<true, kXLMesh> : k_shade_bounce<false, kXLMesh>;
   return xl ? (diff ? k_shade_bounce<true, kXLSpotSphere> : k_shade_bounce<false, kXLSpotSphere>)
             : (diff ? k_shade_bounce<true, kXLNone> : k_shade_bounce<false, kXLNone>);
@@ -4743,6 +5033,7 @@ struct yk_device {
   DBuf<uint2> ml_nodes;
   DBuf<uint32_t> ml_leaf;
   bool diff_only = false;  // every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>)
+  bool glossy = false;     // a material is glossy: the shading kernels' GL instantiations
   yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
   void* abort_user = nullptr;
   bool big_leaves = false;  // the resident tree has a leaf of 2^17 references or more: *_big kernels
@@ -5071,6 +5362,26 @@ DMat make_mat(const yk_material_state& m) {
     M.emit_col[k] = m.emit_color[k];
   }
   M.double_sided = m.double_sided;
+  M.on = m.oren_nayar ? 1 : 0;
+  M.on_a = m.oren_nayar_a;
+  M.on_b = m.oren_nayar_b;
+  if (m.type == YK_MAT_GLOSSY) {
+    for (int k = 0; k < 3; ++k) {
+      M.col[k] = m.gloss_color[k];
+      M.gl.diff[k] = m.diff_color[k];
+    }
+    M.gl.exponent = m.exponent;
+    M.gl.exp_u = m.exp_u;
+    M.gl.exp_v = m.exp_v;
+    M.gl.m_glossy = m.reflectivity;
+    M.gl.m_diffuse = m.m_diffuse;
+    // initBSDF, glossy.cc:94: std::min(0.6f, x) is (x < 0.6f) ? x : 0.6f, so a NaN x gives 0.6
+    const float x = 1.f - (m.reflectivity / (m.reflectivity + (1.f - m.reflectivity) * m.m_diffuse));
+    M.gl.p_diffuse = (x < 0.6f) ? x : 0.6f;
+    M.gl.with_diffuse = m.with_diffuse ? 1 : 0;
+    M.gl.anisotropic = m.anisotropic ? 1 : 0;
+    return M;
+  }
   for (int k = 0; k < 3; ++k) M.mirror[k] = m.mirror_color[k];
   M.ncomp = std::max(0, std::min(4, (int)m.ncomp));
   for (int i = 0; i < 4; ++i) {
@@ -5082,9 +5393,6 @@ DMat make_mat(const yk_material_state& m) {
   M.tfilter = m.transmit_filter;
   M.fresnel = m.has_fresnel;
   M.ior2 = m.ior_squared;
-  M.on = m.oren_nayar ? 1 : 0;
-  M.on_a = m.oren_nayar_a;
-  M.on_b = m.oren_nayar_b;
   return M;
 }
 
@@ -5601,9 +5909,13 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   {  // the shading kernels' diffuse-only instantiation (mat_sample<true>); YK_DIFF=0 never
     const char* e = std::getenv("YK_DIFF");
     d->diff_only = !(e && std::atoi(e) == 0);
-    for (const DMat& m : mats)
-      if (!(m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on)))
+    d->glossy = false;
+    for (const DMat& m : mats) {
+      if (m.type == YK_MAT_GLOSSY) d->glossy = true;  // never diffuse-only: mat_sample<true> is shinydiffuse's
+      if (m.type == YK_MAT_GLOSSY ||
+          !(m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on)))
         d->diff_only = false;
+    }
   }
   // mesh lights: check every light's tree before anything of them is resident
   // (a tree deeper than the shading kernels' per-lane stack is refused, not cut)

@@ -51,10 +51,22 @@ int yk_scene_create(yk_scene** out) {
 
 void yk_scene_destroy(yk_scene* s) { delete s; }
 
+namespace {
+bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+}  // namespace
+
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material: NULL argument");
-  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT)
+  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");
+  if (m->type == YK_MAT_GLOSSY) {
+    if (!finite3(m->color) || !finite3(m->diffuse_color) || !std::isfinite(m->glossy_reflect) ||
+        !std::isfinite(m->diffuse_reflect) || !std::isfinite(m->exponent) ||
+        (m->anisotropic && !(std::isfinite(m->exp_u) && std::isfinite(m->exp_v))))
+      return set_error(YK_ERR_ARG, "yk_scene_add_material: glossy colours, reflect strengths and exponents must be finite");
+    if (!m->as_diffuse)
+      return set_error(YK_ERR_UNSUPPORTED, "glossy with as_diffuse = false (BSDF_GLOSSY) is not on the GPU path");
+  }
   if (m->diffuse_brdf != YK_BRDF_LAMBERT && m->diffuse_brdf != YK_BRDF_OREN_NAYAR)
     return set_error(YK_ERR_ARG, "yk_scene_add_material: diffuse_brdf must be YK_BRDF_LAMBERT or YK_BRDF_OREN_NAYAR");
   YK_GUARD_BEGIN
@@ -66,8 +78,22 @@ int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
 
 int yk_scene_add_material_state(yk_scene* s, const yk_material_state* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material_state: NULL argument");
-  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT)
+  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");
+  if (m->type == YK_MAT_GLOSSY) {
+    if (!finite3(m->gloss_color) || !finite3(m->diff_color) || !std::isfinite(m->reflectivity) ||
+        !std::isfinite(m->m_diffuse) || !std::isfinite(m->exponent) ||
+        (m->anisotropic && !(std::isfinite(m->exp_u) && std::isfinite(m->exp_v))))
+      return set_error(YK_ERR_ARG,
+                       "yk_scene_add_material_state: glossy colours, reflect strengths and exponents must be finite");
+    if (!m->as_diffuse)
+      return set_error(YK_ERR_UNSUPPORTED, "glossy with as_diffuse = false (BSDF_GLOSSY) is not on the GPU path");
+    // glossy.cc:69-79 with as_diffuse: BSDF_DIFFUSE | BSDF_REFLECT and nothing else. The device
+    // record keeps glossy's members over shinydiffuse's, so no other flag may steer a kernel there.
+    if (m->bsdf_flags != (0x4u | 0x10u))
+      return set_error(YK_ERR_ARG,
+                       "yk_scene_add_material_state: a glossy state's bsdf_flags must be BSDF_DIFFUSE | BSDF_REFLECT");
+  }
   if (m->oren_nayar != 0 && m->oren_nayar != 1)
     return set_error(YK_ERR_ARG, "yk_scene_add_material_state: oren_nayar must be 0 or 1");
   YK_GUARD_BEGIN

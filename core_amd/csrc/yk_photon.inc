@@ -283,6 +283,7 @@ struct PhotonBuf {
 };
 
 // material_t::getReflectivity, material.cc:48-66
+template <bool GL = false>
 __device__ __forceinline__ c3 get_reflectivity(const DMat& M, const SurfPt& sp, unsigned flags) {
   if (!(flags & (BSDF_TRANSMIT | BSDF_REFLECT) & M.flags)) return C3(0.f, 0.f, 0.f);
   float W = 0.f;
@@ -296,7 +297,7 @@ __device__ __forceinline__ c3 get_reflectivity(const DMat& M, const SurfPt& sp, 
     v3 wi = V3(0.f, 0.f, 0.f);
     float pdf;
     bool ok;
-    const c3 col = mat_sample(M, sp, wo, wi, s3, s4, flags, pdf, W, ok);
+    const c3 col = mat_sample<false, GL>(M, sp, wo, wi, s3, s4, flags, pdf, W, ok);
     total = cadd(total, C3(col.r * W, col.g * W, col.b * W));
   }
   return C3(total.r * 0.0625f, total.g * 0.0625f, total.b * 0.0625f);
@@ -382,6 +383,8 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_emit(PhotonConst PC,
 
 // One hit of every live photon path (photonintegr.cc:256-314): deposit on a
 // diffuse surface, radiance-point data, and scatterPhoton for the next segment.
+// GL (here and below): the scene holds a glossy material, as in the shading kernels.
+template <bool GL = false>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_hit(DScene S, PhotonConst PC, PhotonBuf PB, int bounce,
                                                     const unsigned long long* __restrict__ in_w, int qin,
                                                     unsigned long long* __restrict__ out_w) {
@@ -424,8 +427,8 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_hit(DScene S, Photon
         store4(&PB.s_col[slot], pcol);
         if (PC.final_gather && !caustic && !PC.caustic_pass) {
           store4(&PB.s_nrm[slot], face_forward(sp.Ng, sp.N, wi));
-          store4(&PB.s_refl[slot], get_reflectivity(M, sp, BSDF_DIFFUSE | BSDF_GLOSSY | BSDF_REFLECT));
-          store4(&PB.s_trn[slot], get_reflectivity(M, sp, BSDF_DIFFUSE | BSDF_GLOSSY | BSDF_TRANSMIT));
+          store4(&PB.s_refl[slot], get_reflectivity<GL>(M, sp, BSDF_DIFFUSE | BSDF_GLOSSY | BSDF_REFLECT));
+          store4(&PB.s_trn[slot], get_reflectivity<GL>(M, sp, BSDF_DIFFUSE | BSDF_GLOSSY | BSDF_TRANSMIT));
         }
       }
       if (bounce < PC.max_bounces) {
@@ -441,7 +444,7 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_hit(DScene S, Photon
         const unsigned sflags = PC.caustic_pass == 2 ? (BSDF_SPECULAR | BSDF_REFLECT | BSDF_TRANSMIT | BSDF_GLOSSY |
                                                         BSDF_FILTER | BSDF_DISPERSIVE)
                                                      : BSDF_ALL;
-        const c3 scol = mat_sample(M, sp, wi, wo, s5, s6, sflags, pdf, W, ok, sfl);
+        const c3 scol = mat_sample<false, GL>(M, sp, wi, wo, s5, s6, sflags, pdf, W, ok, sfl);
         if (pdf > 1.0e-6f) {
           c3 cnew = cmul(cmul(pcol, C3(1.f, 1.f, 1.f)), scol);
           cnew = C3(cnew.r * W, cnew.g * W, cnew.b * W);
@@ -519,6 +522,7 @@ struct PMConst {
 // photonIntegrator_t::integrate after estimateAllDirectLight
 // (photonintegr.cc:819-866): show_map lookups and the direct diffuse-map
 // estimate of the non-final-gather mode.
+template <bool GL = false>
 __global__ void __launch_bounds__(64) k_pm_post(DScene S, Batch B, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
@@ -548,7 +552,7 @@ __global__ void __launch_bounds__(64) k_pm_post(DScene S, Batch B, PMConst PM, l
       for (int k = 0; k < ng; ++k) {
         const int d = f[k].idx;
         const float4 w = PM.dmap.dir[d], pc = PM.dmap.col[d];
-        const c3 surf = mat_eval(M, sp, wo, V3(w.x, w.y, w.z));
+        const c3 surf = mat_eval<true, GL>(M, sp, wo, V3(w.x, w.y, w.z));
         col = cadd(col, cmul(C3(surf.r * scale, surf.g * scale, surf.b * scale), C3(pc.x, pc.y, pc.z)));
       }
     }
@@ -563,7 +567,7 @@ enum : int { FG_ADD = 16, FG_EMIT = 32, FG_CAUS = 64, FG_SPECF = 128 };
 
 // "Zero'th" FG bounce of gather path isub (photonintegr.cc:660-684): sample
 // the camera hit's BSDF; a black weight skips the path.
-template <bool DIFF>
+template <bool DIFF, bool GL = false>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B, RenderConst R, long long nc, int isub,
                                                   float* __restrict__ fg_lcol, unsigned long long* __restrict__ qword) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -582,7 +586,7 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B,
     float pdf, W = B.wlast[c];
     bool ok;
     v3 pdir = V3(0.f, 0.f, 0.f);
-    c3 scol = mat_sample<DIFF>(c_mats[sp.mat], sp, vneg(dir), pdir, s1, s2, BSDF_DIFFUSE | BSDF_REFLECT | BSDF_TRANSMIT,
+    c3 scol = mat_sample<DIFF, GL>(c_mats[sp.mat], sp, vneg(dir), pdir, s1, s2, BSDF_DIFFUSE | BSDF_REFLECT | BSDF_TRANSMIT,
                                pdf, W, ok);
     B.wlast[c] = W;
     scol = C3(scol.r * W, scol.g * W, scol.b * W);
@@ -615,7 +619,7 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B,
 #ifndef YK_FG_WAVES_D
 #define YK_FG_WAVES_D 1  // occupancy target of the diffuse-only k_fg_hit (1: the compiler's choice)
 #endif
-template <bool DIFF>
+template <bool DIFF, bool GL = false>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(DIFF ? YK_FG_WAVES_D : 1)))
 k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
                                                 const unsigned long long* __restrict__ qin_word, int it, int isub,
@@ -684,7 +688,7 @@ k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
               hal_start(h2, 2u, (unsigned)((int)offs - 1));
               int lnum = (int)(hal_next(h2) * (float)R.nlights);
               if (lnum > R.nlights - 1) lnum = R.nlights - 1;
-              nr = gen_light<DIFF>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
+              nr = gen_light<DIFF, kXLNone, GL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
               kend = c_lights[lnum].nslots;
               if (nr) put_org(B, c, sp.P);
               B.lsel[c] = lnum;
@@ -718,7 +722,7 @@ k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
         v3 ndir = dir;
         unsigned sfl;
         const unsigned fl = close ? BSDF_ALL : (BSDF_SPECULAR | BSDF_REFLECT | BSDF_TRANSMIT | BSDF_FILTER);
-        c3 sc = mat_sample<DIFF>(M, sp, pwo, ndir, s1, s2, fl, pdf, W, ok, sfl);
+        c3 sc = mat_sample<DIFF, GL>(M, sp, pwo, ndir, s1, s2, fl, pdf, W, ok, sfl);
         B.wlast[c] = W;
         if (pdf > 1.0e-6f) {
           sc = C3(sc.r * W, sc.g * W, sc.b * W);
@@ -895,6 +899,7 @@ __global__ void __launch_bounds__(256) k_fg_resolve(Batch B, RenderConst R,
 // mcIntegrator_t::estimateCausticPhotons (mcintegrator.cc:384-419, kernel()
 // sample_utils.h:27-31) at the hit of entry c; the caller checks
 // causticMap.ready() (cmap.n > 0).
+template <bool GL = false>
 __device__ __forceinline__ c3 caustic_estimate(const DScene& S, const Batch& B, const PMConst& PM, long long c) {
   const yk_ray r = B.p_rays[c];
   const v3 from = V3(r.from[0], r.from[1], r.from[2]), dir = V3(r.dir[0], r.dir[1], r.dir[2]);
@@ -910,7 +915,7 @@ __device__ __forceinline__ c3 caustic_estimate(const DScene& S, const Batch& B, 
     for (int k = 0; k < ng; ++k) {
       const int d = f[k].idx;
       const float4 w = PM.cmap.dir[d], pc = PM.cmap.col[d];
-      const c3 surf = mat_eval(M, sp, wo, V3(w.x, w.y, w.z));
+      const c3 surf = mat_eval<true, GL>(M, sp, wo, V3(w.x, w.y, w.z));
       const float s = 1.f - f[k].d2 * g;
       const float kk = (float)((((double)(3.f * g) * YK_1_PI_D) * (double)s) * (double)s);
       sum = cadd(sum, cmul(C3(surf.r * kk, surf.g * kk, surf.b * kk), C3(pc.x, pc.y, pc.z)));
@@ -923,6 +928,7 @@ __device__ __forceinline__ c3 caustic_estimate(const DScene& S, const Batch& B, 
 
 // col += finalGathering (pathCol / nSampl) and col += estimateCausticPhotons
 // in the order photonIntegrator_t::integrate adds them (photonintegr.cc:827-852).
+template <bool GL = false>
 __global__ void __launch_bounds__(64) k_pm_finish(DScene S, Batch B, RenderConst R, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc || !(B.prim_hit[c] & PH_DIFFUSE)) return;
@@ -931,7 +937,7 @@ __global__ void __launch_bounds__(64) k_pm_finish(DScene S, Batch B, RenderConst
     const float ns = (float)R.nsub;
     col = cadd(col, C3(B.pathcol[3 * c] / ns, B.pathcol[3 * c + 1] / ns, B.pathcol[3 * c + 2] / ns));
   }
-  if (PM.cmap.n > 0) col = cadd(col, caustic_estimate(S, B, PM, c));  // causticMap.ready()
+  if (PM.cmap.n > 0) col = cadd(col, caustic_estimate<GL>(S, B, PM, c));  // causticMap.ready()
   B.col[3 * c] = col.r;
   B.col[3 * c + 1] = col.g;
   B.col[3 * c + 2] = col.b;
@@ -940,10 +946,11 @@ __global__ void __launch_bounds__(64) k_pm_finish(DScene S, Batch B, RenderConst
 // pathIntegrator_t::integrate with caustic_type photon / both: col +=
 // estimateCausticPhotons right after estimateAllDirectLight on a diffuse hit
 // (pathtracer.cc:168-172), before the path samples are added.
+template <bool GL = false>
 __global__ void __launch_bounds__(64) k_pt_caustic(DScene S, Batch B, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc || !(B.prim_hit[c] & PH_DIFFUSE)) return;
-  const c3 sum = caustic_estimate(S, B, PM, c);
+  const c3 sum = caustic_estimate<GL>(S, B, PM, c);
   B.col[3 * c] = B.col[3 * c] + sum.r;
   B.col[3 * c + 1] = B.col[3 * c + 1] + sum.g;
   B.col[3 * c + 2] = B.col[3 * c + 2] + sum.b;

@@ -104,6 +104,64 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   o[YK_LIGHT_PROBE_TRI] = (float)tri;
 }
 
+// yk_debug_material_probe: mat_eval / mat_sample / mat_pdf with glossy's code
+// compiled in (GL), on material mi of the bound constants at a flat surface
+// point; fpow_ref and the device library's atanf / tanf on their own
+__global__ void k_material_probe(int mi, int fn, const float* in, long long n, float* out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* x = in + YK_MATERIAL_PROBE_IN * i;
+  float* o = out + YK_MATERIAL_PROBE_OUT * i;
+  for (int k = 0; k < YK_MATERIAL_PROBE_OUT; ++k) o[k] = 0.f;
+  if (fn == YK_MATERIAL_PROBE_FPOW) {
+    o[0] = fpow_ref(x[0], x[1]);
+    o[1] = flog2_ref(x[0]);
+    o[2] = fexp2_ref(x[1]);
+    return;
+  }
+  if (fn == YK_MATERIAL_PROBE_ATAN_TAN) {
+    o[0] = atanf(x[0]);
+    o[1] = tanf(x[0]);
+    return;
+  }
+  const DMat& M = c_mats[mi];
+  SurfPt sp{};
+  sp.N = sp.Ng = ld3(x);
+  sp.mat = mi;
+  if (x[19] != 0.f) {
+    sp.NU = ld3(x + 13);
+    sp.NV = ld3(x + 16);
+  } else {
+    create_cs(sp.N, sp.NU, sp.NV);
+  }
+  const v3 wo = ld3(x + 3);
+  const unsigned flags = (unsigned)x[9];
+  if (fn == YK_MATERIAL_PROBE_EVAL) {
+    const c3 col = M.type == YK_MAT_GLOSSY ? glossy_eval(M, sp, wo, ld3(x + 6), flags) : mat_eval(M, sp, wo, ld3(x + 6));
+    o[0] = col.r;
+    o[1] = col.g;
+    o[2] = col.b;
+  } else if (fn == YK_MATERIAL_PROBE_SAMPLE) {
+    v3 wi = V3(0.f, 0.f, 0.f);
+    float pdf = 0.f, W = 0.f;
+    bool ok;
+    unsigned sfl;
+    const c3 col = mat_sample<false, true>(M, sp, wo, wi, x[6], x[7], flags, pdf, W, ok, sfl);
+    o[0] = ok ? 1.f : 0.f;
+    o[1] = wi.x;
+    o[2] = wi.y;
+    o[3] = wi.z;
+    o[4] = col.r;
+    o[5] = col.g;
+    o[6] = col.b;
+    o[7] = pdf;
+    o[8] = W;
+    o[9] = (float)sfl;
+  } else {
+    o[0] = M.type == YK_MAT_GLOSSY ? glossy_pdf(M, sp, wo, ld3(x + 6), flags) : mat_pdf(M, sp, wo, ld3(x + 6));
+  }
+}
+
 // yk_debug_camera_rays: cam_shoot of the bound camera's kind, the function
 // k_camera calls, on host-supplied film positions and lens samples
 template <int KIND>
@@ -142,6 +200,34 @@ extern "C" int yk_debug_camera_rays(yk_device* d, const float* pxy_lens, int64_t
   HIPCHK(hipStreamSynchronize(d->stream));
   HIPCHK(hipMemcpy(rays_out, drays.p, (size_t)n * sizeof(yk_ray), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(wt_out, dwt.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t fn, const float* in, int64_t n,
+                                       float* out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_material_probe: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !in || !out || n < 0 || n > (1ll << 24))
+    return set_error(YK_ERR_ARG, "yk_debug_material_probe: bad arguments");
+  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_material_probe: no scene uploaded");
+  if (mat_index < 0 || mat_index >= (int32_t)d->mats_host.size())
+    return set_error(YK_ERR_ARG, "yk_debug_material_probe: no such material");
+  if (fn < YK_MATERIAL_PROBE_EVAL || fn > YK_MATERIAL_PROBE_ATAN_TAN)
+    return set_error(YK_ERR_ARG, "yk_debug_material_probe: unknown function");
+  if (n == 0) return YK_OK;
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  bind_constants(d);
+  DBuf<float> din, dout;
+  din.ensure((size_t)n * YK_MATERIAL_PROBE_IN);
+  dout.ensure((size_t)n * YK_MATERIAL_PROBE_OUT);
+  HIPCHK(hipMemcpy(din.p, in, (size_t)n * YK_MATERIAL_PROBE_IN * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_material_probe, dim3(grid_for(n)), dim3(256), 0, d->stream, (int)mat_index, (int)fn,
+                     (const float*)din.p, (long long)n, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(out, dout.p, (size_t)n * YK_MATERIAL_PROBE_OUT * sizeof(float), hipMemcpyDeviceToHost));
   return YK_OK;
   YK_GUARD_END
 }

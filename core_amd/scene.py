@@ -31,17 +31,26 @@ class Scene:
         return self._p
 
     # -- assembly ------------------------------------------------------
-    def add_material(self, type_=A.YK_MAT_SHINYDIFFUSE, color=(1, 1, 1), diffuse_reflect=1.0, emit=0.0,
+    def add_material(self, type_=A.YK_MAT_SHINYDIFFUSE, color=(1, 1, 1), diffuse_reflect=None, emit=0.0,
                      power=1.0, double_sided=False, mirror_color=(1, 1, 1), specular_reflect=0.0,
                      transparency=0.0, translucency=0.0, transmit_filter=1.0, fresnel_effect=False, ior=1.33,
-                     diffuse_brdf="lambert", sigma=0.1):
+                     diffuse_brdf="lambert", sigma=0.1, diffuse_color=(1, 1, 1), glossy_reflect=1.0,
+                     exponent=50.0, as_diffuse=True, anisotropic=False, exp_u=50.0, exp_v=50.0):
         """shinydiffusemat / light_mat parameters with the reference factory defaults
         (shinydiffuse.cc:474-514, simple.cc:80-90); diffuse_brdf "oren_nayar"
-        with roughness sigma (shinydiffuse.cc:505-514)."""
-        brdf = {"lambert": A.YK_BRDF_LAMBERT, "oren_nayar": A.YK_BRDF_OREN_NAYAR}[diffuse_brdf]
+        with roughness sigma (shinydiffuse.cc:505-514).
+        type_ = A.YK_MAT_GLOSSY: glossy (glossy.cc:353-389) -- color is the gloss colour,
+        diffuse_reflect defaults to 0 for it (1 for the other kinds), and
+        diffuse_color, glossy_reflect, exponent, as_diffuse, anisotropic, exp_u, exp_v
+        are its own; "Oren-Nayar" is accepted as the reference spells it for this kind."""
+        brdf = {"lambert": A.YK_BRDF_LAMBERT, "oren_nayar": A.YK_BRDF_OREN_NAYAR,
+                "Oren-Nayar": A.YK_BRDF_OREN_NAYAR}[diffuse_brdf]
+        if diffuse_reflect is None:
+            diffuse_reflect = 0.0 if type_ == A.YK_MAT_GLOSSY else 1.0
         m = A.yk_material(type_, A.f3(*color), diffuse_reflect, emit, power, int(double_sided),
                           A.f3(*mirror_color), specular_reflect, transparency, translucency, transmit_filter,
-                          int(fresnel_effect), ior, brdf, sigma)
+                          int(fresnel_effect), ior, brdf, sigma, A.f3(*diffuse_color), glossy_reflect, exponent,
+                          int(as_diffuse), int(anisotropic), exp_u, exp_v)
         mid = C.c_int32()
         A.check(A.lib().yk_scene_add_material(self._p, C.byref(m), C.byref(mid)))
         return mid.value

@@ -41,7 +41,7 @@ extern "C" {
 
 /* ---- scene description (POD mirrors of the reference paraMap_t params) ---- */
 
-enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1 };
+enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1, YK_MAT_GLOSSY = 2 };
 typedef struct yk_material {
   int32_t type;           /* YK_MAT_*                                               */
   float color[3];         /* "color"  shinydiffuse.cc:474,483 / simple.cc:82        */
@@ -64,6 +64,21 @@ typedef struct yk_material {
    * initOrenNayar(sigma), shinydiffuse.cc:170-176 */
   int32_t diffuse_brdf;
   double sigma;
+  /* glossy (glossyMat_t::factory, glossy.cc:353-389). Appended fields only: the
+   * offsets above are what earlier callers compiled against, and the other
+   * kinds do not read the tail. For YK_MAT_GLOSSY `color` is the gloss colour
+   * ("color" [1,1,1]), `diffuse_reflect` is "diffuse_reflect" [0 for glossy; > 0
+   * adds the diffuse base], and diffuse_brdf YK_BRDF_OREN_NAYAR ("Oren-Nayar")
+   * with sigma [0.1] is glossy's own initOrenNayar (glossy.cc:97-103). A
+   * zero-initialised struct must set the bracketed defaults. as_diffuse == 0
+   * (BSDF_GLOSSY, the glossy branch of recursiveRaytrace) is not on the path:
+   * YK_ERR_UNSUPPORTED. */
+  float diffuse_color[3]; /* "diffuse_color" [1,1,1]                                */
+  float glossy_reflect;   /* "glossy_reflect" [1]                                   */
+  float exponent;         /* "exponent" [50]                                        */
+  int32_t as_diffuse;     /* "as_diffuse" [1]                                       */
+  int32_t anisotropic;    /* "anisotropic" [0]: exp_u / exp_v instead of exponent   */
+  float exp_u, exp_v;     /* "exp_u" [50], "exp_v" [50]                             */
 } yk_material;
 enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 
@@ -324,6 +339,11 @@ const char* yk_version(void);
 /* ---- host scene (scene_t geometry state machine + update) ---- */
 int yk_scene_create(yk_scene** out);
 void yk_scene_destroy(yk_scene* s);
+/* YK_ERR_UNSUPPORTED for an unknown type and for a glossy material with
+ * as_diffuse == 0; YK_ERR_ARG for a glossy material with a non-finite colour,
+ * glossy_reflect, diffuse_reflect or exponent (yk_scene_add_material_state
+ * likewise, for the state's members, and for a glossy state whose bsdf_flags
+ * are not exactly BSDF_DIFFUSE | BSDF_REFLECT) */
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out);
 /* one TRIM mesh: points xyz (npoints*3), faces abc (nfaces*3); startTriMesh +
  * addVertex* + addTriangle* + endTriMesh (scene.cc:265-320,520-625) */
@@ -441,6 +461,17 @@ typedef struct yk_material_state {
   int32_t oren_nayar;       /* mUseOrenNayar                                             */
   float oren_nayar_a;       /* mOrenNayar_A = 1 - 0.5 s^2/(s^2 + 0.33), in double        */
   float oren_nayar_b;       /* mOrenNayar_B = 0.45 s^2/(s^2 + 0.09), in double           */
+  /* glossyMat_t members after its constructor and factory (glossy.cc:56-62);
+   * appended, zero for the other kinds. For YK_MAT_GLOSSY bsdf_flags are what
+   * glossy.cc:69-79 sets, oren_nayar / _a / _b are orenNayar / orenA / orenB of
+   * glossyMat_t::initOrenNayar, and the shinydiffuse members above are zero.
+   * exp_u / exp_v are read only when anisotropic (the constructor leaves them
+   * unset otherwise; they are stored as given). */
+  float gloss_color[3], diff_color[3];
+  float exponent, exp_u, exp_v;
+  float reflectivity;       /* "glossy_reflect": MDat_t::mGlossy without shader nodes     */
+  float m_diffuse;          /* mDiffuse                                                  */
+  int32_t as_diffuse, with_diffuse, anisotropic;
 } yk_material_state;
 
 typedef struct yk_area_light_state { /* areaLight_t members (arealight.h:45-53) */
@@ -710,8 +741,9 @@ int yk_device_export_tree(yk_device* d, uint32_t* nodes, int64_t node_cap, uint3
                           int64_t* nnodes_out, int64_t* nleaf_out);
 /* Test-only hooks (the watchdog's tree damage, the lights' function probe)
  * are declared in yk_test_hooks.h, yk_test_hooks_light.h,
- * yk_test_hooks_camera.h, yk_test_hooks_film.h and yk_test_hooks_depth.h, not
- * here, and are disabled unless YK_DEBUG_HOOKS=1. */
+ * yk_test_hooks_camera.h, yk_test_hooks_film.h, yk_test_hooks_depth.h and
+ * yk_test_hooks_material.h, not here, and are disabled unless
+ * YK_DEBUG_HOOKS=1. */
 
 #ifdef __cplusplus
 }
