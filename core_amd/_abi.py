@@ -15,6 +15,7 @@ YK_OK = 0
 YK_ERR_ABORTED = 7
 YK_ERR_ARG, YK_ERR_STATE, YK_ERR_HIP, YK_ERR_UNSUPPORTED, YK_ERR_ALLOC, YK_ERR_INTERNAL = 1, 2, 3, 4, 5, 6
 YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT, YK_MAT_GLOSSY = 0, 1, 2
+YK_MAT_COATED_GLOSSY = 4  # 3 is unassigned and refused
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_LIGHT_MESH = 5
 YK_MESH_LIGHT_MAX_TRIS, YK_MESH_LIGHT_MAX_DEPTH = 65536, 29
@@ -76,7 +77,9 @@ class yk_material_state(C.Structure):
                 # appended: glossyMat_t's members
                 ("gloss_color", f3), ("diff_color", f3), ("exponent", C.c_float), ("exp_u", C.c_float),
                 ("exp_v", C.c_float), ("reflectivity", C.c_float), ("m_diffuse", C.c_float),
-                ("as_diffuse", C.c_int32), ("with_diffuse", C.c_int32), ("anisotropic", C.c_int32)]
+                ("as_diffuse", C.c_int32), ("with_diffuse", C.c_int32), ("anisotropic", C.c_int32),
+                # appended: coatedGlossyMat_t::IOR
+                ("ior", C.c_float)]
 
 
 class yk_area_light_state(C.Structure):

@@ -47,6 +47,39 @@ yk_material_state material_state(const yk_material& m) {
     o.bsdf_flags = kEmit;
     for (int k = 0; k < 3; ++k) o.color[k] = m.color[k] * m.power;
     o.double_sided = m.double_sided;
+  } else if (m.type == YK_MAT_COATED_GLOSSY) {  // coatedGlossyMat_t ctor + factory, coatedglossy.cc:80-102,420-463
+    for (int k = 0; k < 3; ++k) {
+      o.gloss_color[k] = m.color[k];
+      o.diff_color[k] = m.diffuse_color[k];
+      o.mirror_color[k] = m.mirror_color[k];
+    }
+    double ior = m.ior;
+    if (ior == 1.f) ior = 1.0000001f;  // coatedglossy.cc:441, as written
+    o.ior = (float)ior;                // PFLOAT IOR
+    o.exponent = m.exponent;
+    o.reflectivity = m.glossy_reflect;
+    o.m_diffuse = m.diffuse_reflect;
+    o.as_diffuse = m.as_diffuse ? 1 : 0;
+    o.comp_flags[0] = kSpecular | kReflect;
+    o.comp_flags[1] = o.as_diffuse ? (kDiffuse | kReflect) : (kGlossy | kReflect);
+    if (m.diffuse_reflect > 0.f) {
+      o.comp_flags[2] = kDiffuse | kReflect;
+      o.with_diffuse = 1;
+      o.ncomp = 3;
+    } else {
+      o.comp_flags[2] = 0u;  // BSDF_NONE
+      o.ncomp = 2;
+    }
+    o.bsdf_flags = o.comp_flags[0] | o.comp_flags[1] | o.comp_flags[2];
+    o.anisotropic = m.anisotropic ? 1 : 0;
+    o.exp_u = m.exp_u;
+    o.exp_v = m.exp_v;
+    if (m.diffuse_brdf == YK_BRDF_OREN_NAYAR) {  // coatedGlossyMat_t::initOrenNayar(sigma), coatedglossy.cc:119-125
+      const double sigma2 = m.sigma * m.sigma;
+      o.oren_nayar = 1;
+      o.oren_nayar_a = (float)(1.0 - 0.5 * (sigma2 / (sigma2 + 0.33)));
+      o.oren_nayar_b = (float)(0.45 * sigma2 / (sigma2 + 0.09));
+    }
   } else if (m.type == YK_MAT_GLOSSY) {  // glossyMat_t ctor + factory, glossy.cc:65-80,353-389 (no shader nodes)
     for (int k = 0; k < 3; ++k) {
       o.gloss_color[k] = m.color[k];

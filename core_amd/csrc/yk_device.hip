@@ -80,6 +80,10 @@ struct DMat {
       float m_diffuse;    // mDiffuse
       float p_diffuse;    // MDat_t::pDiffuse (glossy.cc:94), constant without nodes
       int with_diffuse, anisotropic;
+      // coatedGlossyMat_t (coatedglossy.cc:63-77) holds the same members and two more,
+      // in words the glossy half left free; unread for YK_MAT_GLOSSY
+      float mirror[3];    // mirror_color
+      float ior;          // IOR
     } gl;
   };
   int on;             // mUseOrenNayar (shinydiffuse.cc:170-176) / glossyMat_t::orenNayar
@@ -2102,6 +2106,255 @@ __device__ __forceinline__ float glossy_pdf(const DMat& M, const SurfPt& sp, v3 
   return pdf;
 }
 
+// ---- coated glossy (coatedGlossyMat_t, coatedglossy.cc; fresnel(), vector3d.cc:110-137) ----
+// The glossy base seen through a dielectric coat that reflects perfectly with
+// a Fresnel weight. In source order, like glossy: no reference output holds
+// the material. Its record is the glossy half of DMat plus gl.mirror / gl.ior.
+
+// fresnel(), vector3d.cc:110-137: eta*eta + c*c - 1 and 1 + (...) run in float
+// (integer literals), the 0.5*(g-c)*(g-c) product and all that meets it in double
+__device__ __forceinline__ void fresnel_ref(v3 I, v3 n, float IOR, float& Kr, float& Kt) {
+  const float eta = IOR;
+  const v3 N = (vdot(I, n) < 0.f) ? vneg(n) : n;
+  const float c = vdot(I, N);
+  float g = eta * eta + c * c - 1.f;
+  if (g <= 0.f) g = 0.f;
+  else g = sqrtf(g);
+  const float aux = c * (g + c);
+  Kr = (float)((((0.5 * (double)(g - c)) * (double)(g - c)) / (double)((g + c) * (g + c))) *
+               (double)(1.f + ((aux - 1.f) * (aux - 1.f)) / ((aux + 1.f) * (aux + 1.f))));
+  if ((double)Kr < 1.0) Kt = 1.f - Kr;
+  else Kt = 0.f;
+}
+
+// coatedGlossyMat_t::eval, coatedglossy.cc:156-193 (as_diffuse). cos_wi_H is not
+// clamped here (glossy's is); the diffuse base is multiplied by Kt directly,
+// where sample() goes through diffuseReflectFresnel.
+__device__ __forceinline__ c3 coated_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wi, unsigned bsdfs) {
+  if (!(bsdfs & BSDF_DIFFUSE) || (vdot(sp.Ng, wi) * vdot(sp.Ng, wo)) < 0.f) return C3(0.f, 0.f, 0.f);
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  float Kr, Kt;
+  const float wiN = fabsf(vdot(wi, N)), woN = fabsf(vdot(wo, N));
+  fresnel_ref(wo, N, M.gl.ior, Kr, Kt);
+  const v3 H = vnormalize(vadd(wo, wi));
+  const float cos_wi_H = vdot(wi, H);
+  const float glossy =
+      Kt * gl_lobe_d(M, sp, H, vdot(H, N)) * gl_schlick(cos_wi_H, M.gl.m_glossy) / gl_as_divisor(cos_wi_H, woN, wiN);
+  c3 col = cscale(glossy, C3(M.col[0], M.col[1], M.col[2]));
+  if (M.gl.with_diffuse) {
+    const c3 dc = cscale(M.gl.m_diffuse * (1.f - M.gl.m_glossy), C3(M.gl.diff[0], M.gl.diff[1], M.gl.diff[2]));
+    col = cadd(col, cscale(M.on ? gl_oren_nayar(M, wi, wo, N) : 1.f, cscale(Kt, dc)));
+  }
+  return col;
+}
+
+// coatedGlossyMat_t::sample, coatedglossy.cc:195-336 (as_diffuse): three
+// components -- the coat (C_SPECULAR, width Kr), the lobe (C_GLOSSY, width
+// Kt*(1-pDiffuse)) and, with a diffuse base, the base (C_DIFFUSE, width
+// Kt*pDiffuse) -- of which the mask's matches are picked by s1. ok = false
+// where the reference returns before it writes W: black, W untouched, wi
+// written only if the pick had set it by then. s.reverse is never set on this
+// path, so the back-sample members do not exist here.
+__device__ __forceinline__ c3 coated_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2,
+                                            unsigned flags, float& pdf, float& W, bool& ok, unsigned& sflags) {
+  constexpr unsigned kSpec = BSDF_SPECULAR | BSDF_REFLECT, kDiff = BSDF_DIFFUSE | BSDF_REFLECT;
+  const float cos_Ng_wo = vdot(sp.Ng, wo);
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  pdf = 0.f;
+  float Kr, Kt;
+  fresnel_ref(wo, N, M.gl.ior, Kr, Kt);
+  const bool use_spec = (flags & kSpec) == kSpec;
+  const bool use_glossy = (flags & kDiff) == kDiff;                  // cFlags[C_GLOSSY] with as_diffuse
+  const bool use_diffuse = M.gl.with_diffuse && use_glossy;          // nBSDF == 3
+  // the matches in component order: width, running sum and component of each
+  float width[3] = {0.f, 0.f, 0.f}, val[3] = {0.f, 0.f, 0.f};
+  int cidx[3] = {0, 0, 0};
+  float sum = 0.f;
+  int nMatch = 0;
+  if (use_spec) {
+    width[nMatch] = Kr;
+    cidx[nMatch] = 0;
+    sum += Kr;
+    val[nMatch++] = sum;
+  }
+  if (use_glossy) {
+    const float a = Kt * (1.f - M.gl.p_diffuse);
+    width[nMatch] = a;
+    cidx[nMatch] = 1;
+    sum += a;
+    val[nMatch++] = sum;
+  }
+  if (use_diffuse) {
+    const float a = Kt * M.gl.p_diffuse;
+    width[nMatch] = a;
+    cidx[nMatch] = 2;
+    sum += a;
+    val[nMatch++] = sum;
+  }
+  if (!nMatch || (double)sum < 0.00001) {
+    ok = false;
+    return C3(0.f, 0.f, 0.f);
+  }
+  int pick = -1;
+  if (nMatch == 1) {
+    pick = 0;
+    width[0] = 1.f;
+  } else {
+    const float inv_sum = 1.f / sum;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (i < nMatch) {
+        val[i] *= inv_sum;
+        width[i] *= inv_sum;
+        if ((s1in <= val[i]) && (pick < 0)) pick = i;
+      }
+    }
+  }
+  if (pick < 0) pick = nMatch - 1;
+  // per-lane picks read through selects, not indexed registers
+  const float wp = pick == 0 ? width[0] : (pick == 1 ? width[1] : width[2]);
+  const float vprev = pick == 1 ? val[0] : val[1];
+  const int comp = pick == 0 ? cidx[0] : (pick == 1 ? cidx[1] : cidx[2]);
+  float s1;
+  if (pick > 0) s1 = (s1in - vprev) / wp;
+  else s1 = s1in / wp;
+  // width[rcIndex[C_GLOSSY]], width[rcIndex[C_DIFFUSE]]
+  const float w_glossy = use_spec ? width[1] : width[0];
+  const float w_diffuse = use_spec ? width[2] : width[1];
+
+  const c3 gcol = C3(M.col[0], M.col[1], M.col[2]), dcol = C3(M.gl.diff[0], M.gl.diff[1], M.gl.diff[2]);
+  if (comp == 0) {  // C_SPECULAR: wi = reflect_dir(N, wo), vector3d.h:297-302
+    const float vn = vdot(wo, N);
+    if (vn < 0.f) {
+      wi = vneg(wo);
+    } else {
+      const float v2 = 2.f * vn;
+      wi = V3(v2 * N.x - wo.x, v2 * N.y - wo.y, v2 * N.z - wo.z);
+    }
+    pdf = wp;
+    W = 1.f;
+    sflags = kSpec;
+    return C3(M.gl.mirror[0] * Kr, M.gl.mirror[1] * Kr, M.gl.mirror[2] * Kr);
+  }
+  v3 Hs = V3(0.f, 0.f, 0.f), H;
+  float cos_wo_H;
+  if (comp == 1) {  // C_GLOSSY
+    Hs = M.gl.anisotropic ? gl_aniso_sample(s1, s2, M.gl.exp_u, M.gl.exp_v) : gl_blinn_sample(s1, s2, M.gl.exponent);
+    H = vadd(vadd(vmul(Hs.x, sp.NU), vmul(Hs.y, sp.NV)), vmul(Hs.z, N));
+    cos_wo_H = vdot(wo, H);
+    if (cos_wo_H < 0.f) {  // H.reflect(N), vector3d.h:288-295
+      const float vn = 2.0f * vdot(H, N);
+      H = V3(vn * N.x - H.x, vn * N.y - H.y, vn * N.z - H.z);
+      cos_wo_H = vdot(wo, H);
+    }
+    {  // reflect_dir(H, wo)
+      const float vn = vdot(wo, H);
+      if (vn < 0.f) {
+        wi = vneg(wo);
+      } else {
+        const float v2 = 2.f * vn;
+        wi = V3(v2 * H.x - wo.x, v2 * H.y - wo.y, v2 * H.z - wo.z);
+      }
+    }
+    if (cos_Ng_wo * vdot(sp.Ng, wi) < 0.f) {
+      ok = false;
+      return C3(0.f, 0.f, 0.f);
+    }
+  } else {  // C_DIFFUSE
+    wi = sample_cos_hemisphere(N, sp.NU, sp.NV, s1, s2);
+    if (cos_Ng_wo * vdot(sp.Ng, wi) < 0.f) {
+      ok = false;
+      return C3(0.f, 0.f, 0.f);
+    }
+    // use[C_GLOSSY] holds whenever the base matched: both carry DIFFUSE | REFLECT
+    H = vnormalize(vadd(wi, wo));
+    Hs = V3(vdot(H, sp.NU), vdot(H, sp.NV), vdot(H, N));
+    cos_wo_H = vdot(wo, H);
+  }
+  const float woN = fabsf(vdot(wo, N));
+  const float wiN = fabsf(vdot(wi, N));
+  float glossy;
+  if (M.gl.anisotropic) {
+    const float D = gl_aniso_d(Hs, M.gl.exp_u, M.gl.exp_v);
+    pdf += (D / gl_pdf_divisor(cos_wo_H)) * w_glossy;
+    glossy = D * gl_schlick(cos_wo_H, M.gl.m_glossy) / gl_as_divisor(cos_wo_H, woN, wiN);
+  } else {
+    const float D = gl_blinn_d(vdot(H, N), M.gl.exponent);
+    pdf += (D / gl_pdf_divisor(cos_wo_H)) * w_glossy;
+    glossy = D * gl_schlick(cos_wo_H, M.gl.m_glossy) / gl_as_divisor(cos_wo_H, woN, wiN);
+  }
+  c3 scolor = cscale(glossy * Kt, gcol);
+  if (use_diffuse) {  // diffuseReflectFresnel: Kt * diffuseReflect(...)
+    const c3 dr = cscale(Kt, gl_diffuse_reflect(wiN, woN, M.gl.m_glossy, M.gl.m_diffuse, dcol));
+    scolor = cadd(scolor, cscale(M.on ? gl_oren_nayar(M, wi, wo, N) : 1.f, dr));
+    pdf += wiN * w_diffuse;
+  }
+  W = wiN / (pdf * 0.99f + 0.01f);
+  sflags = kDiff;
+  return scolor;
+}
+
+// coatedGlossyMat_t::pdf, coatedglossy.cc:338-382 (as_diffuse)
+__device__ __forceinline__ float coated_pdf(const DMat& M, const SurfPt& sp, v3 wo, v3 wi, unsigned flags) {
+  constexpr unsigned kSpec = BSDF_SPECULAR | BSDF_REFLECT, kDiff = BSDF_DIFFUSE | BSDF_REFLECT;
+  if ((vdot(sp.Ng, wo) * vdot(sp.Ng, wi)) < 0.f) return 0.f;
+  const v3 N = face_forward(sp.Ng, sp.N, wo);
+  float pdf = 0.f, Kr, Kt;
+  fresnel_ref(wo, N, M.gl.ior, Kr, Kt);
+  float sum = 0.f;
+  int nMatch = 0;
+  if ((flags & kSpec) == kSpec) {
+    sum += Kr;
+    ++nMatch;
+  }
+  if ((flags & kDiff) == kDiff) {
+    const float width = Kt * (1.f - M.gl.p_diffuse);
+    sum += width;
+    const v3 H = vnormalize(vadd(wi, wo));
+    pdf += (gl_lobe_d(M, sp, H, vdot(N, H)) / gl_pdf_divisor(vdot(wo, H))) * width;
+    ++nMatch;
+    if (M.gl.with_diffuse) {
+      const float wd = Kt * M.gl.p_diffuse;
+      sum += wd;
+      pdf += fabsf(vdot(wi, N)) * wd;
+      ++nMatch;
+    }
+  }
+  if (!nMatch || (double)sum < 0.00001) return 0.f;
+  return pdf / sum;
+}
+
+// coatedGlossyMat_t::getSpecular, coatedglossy.cc:384-418. raylevel is
+// state.raylevel, already incremented by recursiveRaytrace: a camera hit is
+// level 1, and beyond level 5 the coat reflects nothing. 1.00001*cos_wo_N and
+// 0.01 - cos_wi_Ng are double products rounded to float where they meet the
+// vector. Never refracts.
+__device__ __forceinline__ void coated_specular(const DMat& M, const SurfPt& sp, v3 wo, int raylevel, bool& refl,
+                                                v3& dir, c3& col) {
+  refl = false;
+  const bool outside = vdot(sp.Ng, wo) >= 0.f;
+  const float cos_wo_N = vdot(sp.N, wo);
+  v3 N = sp.N, Ng = sp.Ng;
+  if (outside ? !(cos_wo_N >= 0.f) : !(cos_wo_N <= 0.f)) {
+    const float f = (float)(1.00001 * (double)cos_wo_N);
+    N = vnormalize(vsub(sp.N, vmul(f, wo)));
+  }
+  if (!outside) Ng = vneg(sp.Ng);
+  float Kr, Kt;
+  fresnel_ref(wo, N, M.gl.ior, Kr, Kt);
+  if (raylevel > 5) return;
+  const float vn = 2.0f * vdot(wo, N);  // dir[0] = wo; dir[0].reflect(N)
+  v3 w = V3(vn * N.x - wo.x, vn * N.y - wo.y, vn * N.z - wo.z);
+  col = C3(Kr * M.gl.mirror[0], Kr * M.gl.mirror[1], Kr * M.gl.mirror[2]);
+  const float cos_wi_Ng = vdot(w, Ng);
+  if ((double)cos_wi_Ng < 0.01) {
+    const float f = (float)(0.01 - (double)cos_wi_Ng);
+    w = vnormalize(V3(w.x + f * Ng.x, w.y + f * Ng.y, w.z + f * Ng.z));
+  }
+  dir = w;
+  refl = true;
+}
+
 // shinyDiffuseMat_t::eval, shinydiffuse.cc:223-249 (compiled: cos_Ng_wl as
 // (y + z) + x; mD = ((1-c2)*c3)*mT), then mD *= OrenNayar(wo, wl, N) (:247).
 // ON = false: the scene has no Oren-Nayar material (the diffuse-only
@@ -2109,11 +2362,19 @@ __device__ __forceinline__ float glossy_pdf(const DMat& M, const SurfPt& sp, v3 
 // GL = true: the scene holds a glossy material; only then is glossy's code
 // compiled in (mat_sample and mat_pdf likewise), so every other scene runs
 // the kernels it ran before. bsdfs is BSDF_ALL at every call site.
-template <bool ON = true, bool GL = false>
+// GL is a level: kGLNone, kGLGlossy (true in the instantiations' names), or
+// kGLCoated when the scene holds a coated glossy material as well or instead;
+// only then is the coat's code compiled in, so glossy-only scenes too run the
+// kernels they ran before.
+constexpr int kGLNone = 0, kGLGlossy = 1, kGLCoated = 2;
+template <bool ON = true, int GL = false>
 __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wl) {
   if (M.type == YK_MAT_LIGHT) return C3(0.f, 0.f, 0.f);
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY) return glossy_eval(M, sp, wo, wl, BSDF_ALL);
+    if constexpr (GL == kGLCoated) {
+      if (M.type == YK_MAT_COATED_GLOSSY) return coated_eval(M, sp, wo, wl, BSDF_ALL);
+    }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const float cos_Ng_wl = (sp.Ng.y * wl.y + sp.Ng.z * wl.z) + sp.Ng.x * wl.x;
@@ -2140,7 +2401,7 @@ __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v
 // same float operations on the same values -- sum = 0 + w, the normalisation
 // by 1/sum, s1 / wp -- without the loop's per-lane arrays (the shading
 // kernels' registers).
-template <bool DIFF = false, bool GL = false>
+template <bool DIFF = false, int GL = false>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok, unsigned& sflags) {
   static_assert(!(DIFF && GL), "a scene with a glossy material is never diffuse-only");
@@ -2153,6 +2414,9 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
   }
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY) return glossy_sample(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sflags);
+    if constexpr (GL == kGLCoated) {
+      if (M.type == YK_MAT_COATED_GLOSSY) return coated_sample(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sflags);
+    }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const v3 N = (cos_Ng_wo < 0.f) ? vneg(sp.N) : sp.N;
@@ -2253,7 +2517,7 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
   W = fabsf(vdot(w, sp.N)) / (pdf * 0.99f + 0.01f);
   return sc;
 }
-template <bool DIFF = false, bool GL = false>
+template <bool DIFF = false, int GL = false>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok) {
   unsigned sf;
@@ -2264,12 +2528,16 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
 // bit with bsdfs adds its width to the sum; only diffuse ones add pdf.
 // Called with bsdfs = GLOSSY|DIFFUSE|DISPERSIVE|REFLECT|TRANSMIT, which
 // overlaps every shinydiffuse component.
-template <bool GL = false>
+template <int GL = false>
 __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo, v3 wi) {
   if (M.type == YK_MAT_LIGHT) return 0.f;
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY)
       return glossy_pdf(M, sp, wo, wi, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
+    if constexpr (GL == kGLCoated) {
+      if (M.type == YK_MAT_COATED_GLOSSY)
+        return coated_pdf(M, sp, wo, wi, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
+    }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
   const v3 N = (cos_Ng_wo < 0.f) ? vneg(sp.N) : sp.N;
@@ -2293,11 +2561,20 @@ __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo,
 
 // shinyDiffuseMat_t::getSpecular, shinydiffuse.cc:379-433 (compiled: the
 // backface test as (x + z) + y; reflect() without a sign test; the 0.01
-// grazing correction in double)
+// grazing correction in double). GL: the scene holds a glossy or coated glossy
+// material; a coated one answers with its own getSpecular at recursion level
+// raylevel, and its record is never read through the shinydiffuse members.
+template <int GL = false>
 __device__ __forceinline__ void mat_specular(const DMat& M, const SurfPt& sp, v3 wo, bool& refl, bool& refr,
-                                             v3* dir, c3* col) {
+                                             v3* dir, c3* col, int raylevel = 0) {
   refl = refr = false;
   if (M.type == YK_MAT_LIGHT) return;
+  if constexpr (GL == kGLCoated) {
+    if (M.type == YK_MAT_COATED_GLOSSY) {
+      coated_specular(M, sp, wo, raylevel, refl, dir[0], col[0]);
+      return;
+    }
+  }
   const bool backface = ((sp.Ng.x * wo.x + sp.Ng.z * wo.z) + sp.Ng.y * wo.y) < 0.f;
   const v3 N = backface ? vneg(sp.N) : sp.N;
   const v3 Ng = backface ? vneg(sp.Ng) : sp.Ng;
@@ -3237,7 +3514,7 @@ __device__ __forceinline__ bool light_sampled(const DLight& L) {
   return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.type == YK_LIGHT_MESH || L.soft != 0;
 }
 
-template <bool DIFF, int KIND, bool GL = false>
+template <bool DIFF, int KIND, int GL = false>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
                                            unsigned loffs, unsigned long long& traced,
@@ -3250,7 +3527,7 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
 // XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light) or
 // kXLMesh (it holds a mesh light; ml = DScene::ml): see shade_primary_fn
 constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2;
-template <bool DIFF = false, int XL = kXLNone, bool GL = false>
+template <bool DIFF = false, int XL = kXLNone, int GL = false>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
                                          unsigned long long& traced, const DMat* mats = c_mats,
@@ -3301,7 +3578,7 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 // transparent shadows, which filter the colour first). A sphere light's
 // canIntersect() is false (spherelight.cc:49): no MIS weight on its light
 // samples and no BSDF half, so it owns `samples` slots, not 2 * samples.
-template <bool DIFF, int KIND, bool GL>
+template <bool DIFF, int KIND, int GL>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
                                            unsigned loffs, unsigned long long& traced, const DMeshLight* ml) {
@@ -3421,7 +3698,7 @@ constexpr unsigned kAOFlags = BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_REFLECT;
 // returns early (no component matches, or their widths sum below 1e-5) leaves
 // W = 0 and the previous direction: its term is +0 whatever the ray meets,
 // and the slot traces nothing.
-template <bool DIFF, bool GL = false>
+template <bool DIFF, int GL = false>
 __device__ __forceinline__ int gen_ao(const Batch& B, long long c, const AOConst& A, const DMat& M, const SurfPt& sp,
                                       v3 wo, unsigned pixelSample, unsigned soffs, unsigned long long& traced) {
   const c3 black = C3(0.f, 0.f, 0.f);
@@ -3470,7 +3747,7 @@ __device__ __forceinline__ void flush_shadow(const Batch& B, long long c, int ke
 
 // First segment of sub-path isub from a diffuse camera-ray hit: sample the
 // primary BSDF (pathtracer.cc:169-187). Returns the segment's ray.
-template <bool DIFF = false, bool GL = false>
+template <bool DIFF = false, int GL = false>
 __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const RenderConst& R, long long c,
                                                      const SurfPt& sp, const DMat& M, v3 dir, int isub) {
   const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
@@ -3504,7 +3781,7 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // AO: direct lighting with ambient occlusion (gen_ao) -- an instantiation of
 // its own, so the others carry none of its code; A is read by it alone.
 // GL: the scene holds a glossy material (mat_eval); DIFF is false then.
-template <bool DIFF, int XL, bool AO, bool GL = false>
+template <bool DIFF, int XL, bool AO, int GL = false>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
                                                        unsigned long long* __restrict__ qword, AOConst A) {
   // The material records in LDS: per-lane reads of constant memory (the
@@ -3734,7 +4011,7 @@ __global__ void __launch_bounds__(256) k_resolve_ao(DScene S, Batch B, RenderCon
 
 // First segment of sub-paths isub >= 1 (sub-path 0 is fused into
 // k_shade_primary).
-template <bool DIFF, bool GL = false>
+template <bool DIFF, int GL = false>
 __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch B, RenderConst R, long long nc, int isub,
                                                     unsigned long long* __restrict__ qword) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3765,7 +4042,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
 // (pathtracer.cc:189-298): estimateOneDirectLight shadow rays, emission,
 // and the BSDF sample of the next segment. One thread per live path (entry
 // qi of the input bounce queue, owned by camera sample c).
-template <bool DIFF, int XL, bool GL = false>
+template <bool DIFF, int XL, int GL = false>
 __global__ void __launch_bounds__(bounce_block(DIFF))
 __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES))) k_shade_bounce(DScene S, Batch B, RenderConst R,
                                                       const unsigned long long* __restrict__ qin_word, int depth,
@@ -3902,7 +4179,12 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
 // scene pays for.
 // A glossy material (GL) adds general-material instantiations of its own in
 // the same way, one per XL x AO: glossy's lobe code reaches no other scene.
-inline auto shade_primary_fn(bool diff, int xl, bool ao, bool gl) {
+inline auto shade_primary_fn(bool diff, int xl, bool ao, int gl) {
+  if (gl == kGLCoated) {
+    if (xl == kXLMesh) return ao ? k_shade_primary<false, kXLMesh, true, kGLCoated> : k_shade_primary<false, kXLMesh, false, kGLCoated>;
+    if (xl) return ao ? k_shade_primary<false, kXLSpotSphere, true, kGLCoated> : k_shade_primary<false, kXLSpotSphere, false, kGLCoated>;
+    return ao ? k_shade_primary<false, kXLNone, true, kGLCoated> : k_shade_primary<false, kXLNone, false, kGLCoated>;
+  }
   if (gl) {
     if (xl == kXLMesh) return ao ? k_shade_primary<false, kXLMesh, true, true> : k_shade_primary<false, kXLMesh, false, true>;
     if (xl) return ao ? k_shade_primary<false, kXLSpotSphere, true, true> : k_shade_primary<false, kXLSpotSphere, false, true>;
@@ -3918,7 +4200,10 @@ inline auto shade_primary_fn(bool diff, int xl, bool ao, bool gl) {
   return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, false> : k_shade_primary<false, kXLSpotSphere, false>)
             : (diff ? k_shade_primary<true, kXLNone, false> : k_shade_primary<false, kXLNone, false>);
 }
-inline auto shade_bounce_fn(bool diff, int xl, bool gl) {
+inline auto shade_bounce_fn(bool diff, int xl, int gl) {
+  if (gl == kGLCoated)
+    return xl == kXLMesh ? k_shade_bounce<false, kXLMesh, kGLCoated>
+                         : (xl ? k_shade_bounce<false, kXLSpotSphere, kGLCoated> : k_shade_bounce<false, kXLNone, kGLCoated>);
   if (gl)
     return xl == kXLMesh ? k_shade_bounce<false, kXLMesh, true>
                          : (xl ? k_shade_bounce<false, kXLSpotSphere, true> : k_shade_bounce<false, kXLNone, true>);
@@ -4111,6 +4396,8 @@ __global__ void __launch_bounds__(256) k_finish_spec(Batch B, RenderConst R, Nod
 
 // recursiveRaytrace's specular block for the hits of one chunk: allocate the
 // reflect / refract children (rays from sp.P, tmin MIN_RAYDIST, unbounded).
+// GL: as in the shading kernels (a coated glossy material's getSpecular).
+template <int GL = false>
 __global__ void __launch_bounds__(256) k_spawn(DScene S, Batch B, RenderConst R, NodeStore NS, long long base,
                                                long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4135,7 +4422,7 @@ __global__ void __launch_bounds__(256) k_spawn(DScene S, Batch B, RenderConst R,
   bool refl, refr;
   v3 d[2];
   c3 col[2];
-  mat_specular(M, sp, vneg(dir), refl, refr, d, col);
+  mat_specular<GL>(M, sp, vneg(dir), refl, refr, d, col, lv);
   const bool want[2] = {refl, refr};
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
@@ -5033,7 +5320,7 @@ struct yk_device {
   DBuf<uint2> ml_nodes;
   DBuf<uint32_t> ml_leaf;
   bool diff_only = false;  // every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>)
-  bool glossy = false;     // a material is glossy: the shading kernels' GL instantiations
+  int glossy = 0;          // kGLGlossy: a material is glossy; kGLCoated: one is coated glossy (the kernels' GL level)
   yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
   void* abort_user = nullptr;
   bool big_leaves = false;  // the resident tree has a leaf of 2^17 references or more: *_big kernels
@@ -5365,10 +5652,14 @@ DMat make_mat(const yk_material_state& m) {
   M.on = m.oren_nayar ? 1 : 0;
   M.on_a = m.oren_nayar_a;
   M.on_b = m.oren_nayar_b;
-  if (m.type == YK_MAT_GLOSSY) {
+  if (m.type == YK_MAT_GLOSSY || m.type == YK_MAT_COATED_GLOSSY) {
     for (int k = 0; k < 3; ++k) {
       M.col[k] = m.gloss_color[k];
       M.gl.diff[k] = m.diff_color[k];
+    }
+    if (m.type == YK_MAT_COATED_GLOSSY) {
+      for (int k = 0; k < 3; ++k) M.gl.mirror[k] = m.mirror_color[k];
+      M.gl.ior = m.ior;
     }
     M.gl.exponent = m.exponent;
     M.gl.exp_u = m.exp_u;
@@ -5909,10 +6200,11 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   {  // the shading kernels' diffuse-only instantiation (mat_sample<true>); YK_DIFF=0 never
     const char* e = std::getenv("YK_DIFF");
     d->diff_only = !(e && std::atoi(e) == 0);
-    d->glossy = false;
+    d->glossy = kGLNone;
     for (const DMat& m : mats) {
-      if (m.type == YK_MAT_GLOSSY) d->glossy = true;  // never diffuse-only: mat_sample<true> is shinydiffuse's
-      if (m.type == YK_MAT_GLOSSY ||
+      const bool gl = m.type == YK_MAT_GLOSSY || m.type == YK_MAT_COATED_GLOSSY;
+      if (gl) d->glossy = std::max(d->glossy, m.type == YK_MAT_COATED_GLOSSY ? kGLCoated : kGLGlossy);  // never diffuse-only
+      if (gl ||
           !(m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on)))
         d->diff_only = false;
     }

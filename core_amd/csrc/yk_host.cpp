@@ -57,8 +57,18 @@ bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1])
 
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material: NULL argument");
-  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY)
+  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY &&
+      m->type != YK_MAT_COATED_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");
+  if (m->type == YK_MAT_COATED_GLOSSY) {
+    if (!finite3(m->color) || !finite3(m->diffuse_color) || !finite3(m->mirror_color) ||
+        !std::isfinite(m->glossy_reflect) || !std::isfinite(m->diffuse_reflect) || !std::isfinite(m->exponent) ||
+        !std::isfinite(m->ior) || (m->anisotropic && !(std::isfinite(m->exp_u) && std::isfinite(m->exp_v))))
+      return set_error(YK_ERR_ARG,
+                       "yk_scene_add_material: coated glossy colours, reflect strengths, exponents and IOR must be finite");
+    if (!m->as_diffuse)
+      return set_error(YK_ERR_UNSUPPORTED, "coated glossy with as_diffuse = false (BSDF_GLOSSY) is not on the GPU path");
+  }
   if (m->type == YK_MAT_GLOSSY) {
     if (!finite3(m->color) || !finite3(m->diffuse_color) || !std::isfinite(m->glossy_reflect) ||
         !std::isfinite(m->diffuse_reflect) || !std::isfinite(m->exponent) ||
@@ -78,8 +88,28 @@ int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
 
 int yk_scene_add_material_state(yk_scene* s, const yk_material_state* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material_state: NULL argument");
-  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY)
+  if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY &&
+      m->type != YK_MAT_COATED_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");
+  if (m->type == YK_MAT_COATED_GLOSSY) {
+    if (!finite3(m->gloss_color) || !finite3(m->diff_color) || !finite3(m->mirror_color) ||
+        !std::isfinite(m->reflectivity) || !std::isfinite(m->m_diffuse) || !std::isfinite(m->exponent) ||
+        !std::isfinite(m->ior) || (m->anisotropic && !(std::isfinite(m->exp_u) && std::isfinite(m->exp_v))))
+      return set_error(
+          YK_ERR_ARG,
+          "yk_scene_add_material_state: coated glossy colours, reflect strengths, exponents and IOR must be finite");
+    if (!m->as_diffuse)
+      return set_error(YK_ERR_UNSUPPORTED, "coated glossy with as_diffuse = false (BSDF_GLOSSY) is not on the GPU path");
+    // coatedglossy.cc:84-101 with as_diffuse. The device record keeps the material's members over
+    // shinydiffuse's, so no other flag (BSDF_FILTER, BSDF_EMIT) may steer a kernel there.
+    const uint32_t spec = 0x1u | 0x10u, diff = 0x4u | 0x10u;
+    const bool wd = m->with_diffuse != 0;
+    if (m->bsdf_flags != (spec | diff) || m->ncomp != (wd ? 3 : 2) || m->comp_flags[0] != spec ||
+        m->comp_flags[1] != diff || m->comp_flags[2] != (wd ? diff : 0u))
+      return set_error(YK_ERR_ARG,
+                       "yk_scene_add_material_state: a coated glossy state's bsdf_flags must be BSDF_SPECULAR | "
+                       "BSDF_REFLECT | BSDF_DIFFUSE, with nBSDF and cFlags as its constructor sets them");
+  }
   if (m->type == YK_MAT_GLOSSY) {
     if (!finite3(m->gloss_color) || !finite3(m->diff_color) || !std::isfinite(m->reflectivity) ||
         !std::isfinite(m->m_diffuse) || !std::isfinite(m->exponent) ||

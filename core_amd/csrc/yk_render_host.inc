@@ -448,11 +448,11 @@ void enqueue_photon_mapping(BatchCtx& c, const Batch& Bc, const RenderConst& Rc,
   Pipe& P = *c.P;
   const PMConst& PMC = c.fp->PMC;
   const int fg_bounces = c.p->photon.fg_bounces;
-  if (PMC.show_map || !PMC.final_gather) launch(d->glossy ? k_pm_post<true> : k_pm_post<false>, grid_for(n, 64), 64, 0, P.stream, d->S, Bc, PMC, n);
+  if (PMC.show_map || !PMC.final_gather) launch((d->glossy == kGLCoated ? k_pm_post<kGLCoated> : d->glossy ? k_pm_post<kGLGlossy> : k_pm_post<kGLNone>), grid_for(n, 64), 64, 0, P.stream, d->S, Bc, PMC, n);
   // final gathering (photonintegr.cc:637-790): gather path index outermost,
   // pathCol accumulated across paths in the reference's order
   for (int isub = 0; isub < (Rc.pm_fg ? c.fp->nsub : 0); ++isub) {
-    launch(d->glossy ? k_fg_start<false, true> : (d->diff_only ? k_fg_start<true> : k_fg_start<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
+    launch(d->glossy == kGLCoated ? k_fg_start<false, kGLCoated> : d->glossy ? k_fg_start<false, kGLGlossy> : (d->diff_only ? k_fg_start<true> : k_fg_start<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
            P.stream, d->S, Bc, Rc, n, isub, P.fgl.p, qw(c, isub, 0));
     int qin = 1;
     for (int it = 0; it <= fg_bounces; ++it) {
@@ -460,7 +460,7 @@ void enqueue_photon_mapping(BatchCtx& c, const Batch& Bc, const RenderConst& Rc,
       unsigned long long* out_w = qw(c, isub, it + 1);
       trace(c, true, ray_src(Bc.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, Bc.q_hits[qin], nullptr);
       unsigned long long* lk_w = qw(c, isub, it) + c.fp->qwords_per_batch;  // lookup-queue count
-      launch(d->glossy ? k_fg_hit<false, true> : (d->diff_only ? k_fg_hit<true> : k_fg_hit<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
+      launch(d->glossy == kGLCoated ? k_fg_hit<false, kGLCoated> : d->glossy ? k_fg_hit<false, kGLGlossy> : (d->diff_only ? k_fg_hit<true> : k_fg_hit<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
              P.stream, d->S, Bc, Rc, PMC, in_w, it, isub, qin, P.fgl.p, P.fglen.p, out_w, P.lkq.p, lk_w);
       if (it < fg_bounces) trace_shadow_slots(c, Bc, RayCount{out_w, 0, 0});
       const bool lds = lookup_lds(d);
@@ -471,7 +471,7 @@ void enqueue_photon_mapping(BatchCtx& c, const Batch& Bc, const RenderConst& Rc,
       qin ^= 1;
     }
   }
-  launch(d->glossy ? k_pm_finish<true> : k_pm_finish<false>, grid_for(n, 64), 64, 0, P.stream, d->S, Bc, Rc, PMC, n);
+  launch((d->glossy == kGLCoated ? k_pm_finish<kGLCoated> : d->glossy ? k_pm_finish<kGLGlossy> : k_pm_finish<kGLNone>), grid_for(n, 64), 64, 0, P.stream, d->S, Bc, Rc, PMC, n);
 }
 
 // What follows the direct light at the camera hits: photon mapping's
@@ -481,7 +481,7 @@ void enqueue_post_direct(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, lo
   hipStream_t s = c.P->stream;
   if (fp.pm) enqueue_photon_mapping(c, Bc, Rc, n);
   if (fp.cmap && fp.PMC.cmap.n != 0)  // causticMap.ready()
-    launch(c.d->glossy ? k_pt_caustic<true> : k_pt_caustic<false>, grid_for(n, 64), 64, 0, s, c.d->S, Bc, fp.PMC, n);
+    launch((c.d->glossy == kGLCoated ? k_pt_caustic<kGLCoated> : c.d->glossy ? k_pt_caustic<kGLGlossy> : k_pt_caustic<kGLNone>), grid_for(n, 64), 64, 0, s, c.d->S, Bc, fp.PMC, n);
   if (fp.ao) launch(k_resolve_ao, grid_for(n), 256, 0, s, c.d->S, Bc, Rc, fp.AOC, n);
 }
 
@@ -521,7 +521,7 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   const int bblock = bounce_block(d->diff_only);
   for (int isub = 0; isub < (fp.path ? fp.nsub : 0); ++isub) {
     if (isub > 0)  // sub-path 0's first segment came out of k_shade_primary
-      launch(d->glossy ? k_path_start<false, true> : (d->diff_only ? k_path_start<true> : k_path_start<false>), grid_for(n, YK_BOUNCE_BLOCK), YK_BOUNCE_BLOCK, 0,
+      launch(d->glossy == kGLCoated ? k_path_start<false, kGLCoated> : d->glossy ? k_path_start<false, kGLGlossy> : (d->diff_only ? k_path_start<true> : k_path_start<false>), grid_for(n, YK_BOUNCE_BLOCK), YK_BOUNCE_BLOCK, 0,
              s, d->S, Bc, Rc, n, isub, qw(c, isub, 0));
     int qin = 1;
     for (int depth = 1; depth <= fp.bounces; ++depth) {
@@ -545,7 +545,7 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   if (post_direct_after_bounces) enqueue_post_direct(c, Bc, Rc, n);
   if (d->spec) {
     launch(k_finish_spec, grid_for(n), 256, 0, s, Bc, Rc, c.NS, node_base, n);
-    launch(k_spawn, grid_for(n), 256, 0, s, d->S, Bc, Rc, c.NS, node_base, n);
+    launch(d->glossy == kGLCoated ? k_spawn<kGLCoated> : k_spawn<kGLNone>, grid_for(n), 256, 0, s, d->S, Bc, Rc, c.NS, node_base, n);
   } else if (merged) {  // one any-hit launch for the camera hits and all bounces, then one resolve
     trace_shadow_slots(c, Bc, RayCount{qw(c, 0, 0), 0, 0, fp.plan.regions});
     launch(k_resolve_merged, grid_for(n), 256, 0, s, Bc, Rc, n, fp.bounces);

@@ -131,13 +131,16 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
   if (x[19] != 0.f) {
     sp.NU = ld3(x + 13);
     sp.NV = ld3(x + 16);
+    if (x[19] == 2.f) sp.Ng = ld3(x + 10);  // a geometric normal of its own
   } else {
     create_cs(sp.N, sp.NU, sp.NV);
   }
   const v3 wo = ld3(x + 3);
   const unsigned flags = (unsigned)x[9];
   if (fn == YK_MATERIAL_PROBE_EVAL) {
-    const c3 col = M.type == YK_MAT_GLOSSY ? glossy_eval(M, sp, wo, ld3(x + 6), flags) : mat_eval(M, sp, wo, ld3(x + 6));
+    const c3 col = M.type == YK_MAT_GLOSSY          ? glossy_eval(M, sp, wo, ld3(x + 6), flags)
+                   : M.type == YK_MAT_COATED_GLOSSY ? coated_eval(M, sp, wo, ld3(x + 6), flags)
+                                                    : mat_eval(M, sp, wo, ld3(x + 6));
     o[0] = col.r;
     o[1] = col.g;
     o[2] = col.b;
@@ -146,7 +149,7 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
     float pdf = 0.f, W = 0.f;
     bool ok;
     unsigned sfl;
-    const c3 col = mat_sample<false, true>(M, sp, wo, wi, x[6], x[7], flags, pdf, W, ok, sfl);
+    const c3 col = mat_sample<false, kGLCoated>(M, sp, wo, wi, x[6], x[7], flags, pdf, W, ok, sfl);
     o[0] = ok ? 1.f : 0.f;
     o[1] = wi.x;
     o[2] = wi.y;
@@ -157,8 +160,28 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
     o[7] = pdf;
     o[8] = W;
     o[9] = (float)sfl;
+  } else if (fn == YK_MATERIAL_PROBE_SPECULAR) {
+    bool refl, refr;
+    v3 dir[2] = {V3(0.f, 0.f, 0.f), V3(0.f, 0.f, 0.f)};
+    c3 col[2] = {C3(0.f, 0.f, 0.f), C3(0.f, 0.f, 0.f)};
+    mat_specular<kGLCoated>(M, sp, wo, refl, refr, dir, col, (int)x[9]);
+    o[0] = refl ? 1.f : 0.f;
+    o[1] = dir[0].x;
+    o[2] = dir[0].y;
+    o[3] = dir[0].z;
+    o[4] = col[0].r;
+    o[5] = col[0].g;
+    o[6] = col[0].b;
+    if (M.type == YK_MAT_COATED_GLOSSY) {  // fresnel() on its own, at the face-forwarded normal
+      float Kr, Kt;
+      fresnel_ref(wo, face_forward(sp.Ng, sp.N, wo), M.gl.ior, Kr, Kt);
+      o[7] = Kr;
+      o[8] = Kt;
+    }
   } else {
-    o[0] = M.type == YK_MAT_GLOSSY ? glossy_pdf(M, sp, wo, ld3(x + 6), flags) : mat_pdf(M, sp, wo, ld3(x + 6));
+    o[0] = M.type == YK_MAT_GLOSSY          ? glossy_pdf(M, sp, wo, ld3(x + 6), flags)
+           : M.type == YK_MAT_COATED_GLOSSY ? coated_pdf(M, sp, wo, ld3(x + 6), flags)
+                                            : mat_pdf(M, sp, wo, ld3(x + 6));
   }
 }
 
@@ -213,7 +236,7 @@ extern "C" int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t 
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_material_probe: no scene uploaded");
   if (mat_index < 0 || mat_index >= (int32_t)d->mats_host.size())
     return set_error(YK_ERR_ARG, "yk_debug_material_probe: no such material");
-  if (fn < YK_MATERIAL_PROBE_EVAL || fn > YK_MATERIAL_PROBE_ATAN_TAN)
+  if (fn < YK_MATERIAL_PROBE_EVAL || fn > YK_MATERIAL_PROBE_SPECULAR)
     return set_error(YK_ERR_ARG, "yk_debug_material_probe: unknown function");
   if (n == 0) return YK_OK;
   YK_GUARD_BEGIN

@@ -33,7 +33,7 @@ class Scene:
     # -- assembly ------------------------------------------------------
     def add_material(self, type_=A.YK_MAT_SHINYDIFFUSE, color=(1, 1, 1), diffuse_reflect=None, emit=0.0,
                      power=1.0, double_sided=False, mirror_color=(1, 1, 1), specular_reflect=0.0,
-                     transparency=0.0, translucency=0.0, transmit_filter=1.0, fresnel_effect=False, ior=1.33,
+                     transparency=0.0, translucency=0.0, transmit_filter=1.0, fresnel_effect=False, ior=None,
                      diffuse_brdf="lambert", sigma=0.1, diffuse_color=(1, 1, 1), glossy_reflect=1.0,
                      exponent=50.0, as_diffuse=True, anisotropic=False, exp_u=50.0, exp_v=50.0):
         """shinydiffusemat / light_mat parameters with the reference factory defaults
@@ -42,11 +42,15 @@ class Scene:
         type_ = A.YK_MAT_GLOSSY: glossy (glossy.cc:353-389) -- color is the gloss colour,
         diffuse_reflect defaults to 0 for it (1 for the other kinds), and
         diffuse_color, glossy_reflect, exponent, as_diffuse, anisotropic, exp_u, exp_v
-        are its own; "Oren-Nayar" is accepted as the reference spells it for this kind."""
+        are its own; "Oren-Nayar" is accepted as the reference spells it for this kind.
+        type_ = A.YK_MAT_COATED_GLOSSY: coated_glossy (coatedglossy.cc:420-498) -- the glossy
+        keywords plus mirror_color and ior, which defaults to 1.4 for it (1.33 otherwise)."""
         brdf = {"lambert": A.YK_BRDF_LAMBERT, "oren_nayar": A.YK_BRDF_OREN_NAYAR,
                 "Oren-Nayar": A.YK_BRDF_OREN_NAYAR}[diffuse_brdf]
         if diffuse_reflect is None:
-            diffuse_reflect = 0.0 if type_ == A.YK_MAT_GLOSSY else 1.0
+            diffuse_reflect = 0.0 if type_ in (A.YK_MAT_GLOSSY, A.YK_MAT_COATED_GLOSSY) else 1.0
+        if ior is None:
+            ior = 1.4 if type_ == A.YK_MAT_COATED_GLOSSY else 1.33
         m = A.yk_material(type_, A.f3(*color), diffuse_reflect, emit, power, int(double_sided),
                           A.f3(*mirror_color), specular_reflect, transparency, translucency, transmit_filter,
                           int(fresnel_effect), ior, brdf, sigma, A.f3(*diffuse_color), glossy_reflect, exponent,

@@ -41,7 +41,9 @@ extern "C" {
 
 /* ---- scene description (POD mirrors of the reference paraMap_t params) ---- */
 
-enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1, YK_MAT_GLOSSY = 2 };
+/* Value 3 is unassigned and stays refused (YK_ERR_UNSUPPORTED): callers and
+ * tests rely on it as "a type the path does not know". */
+enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1, YK_MAT_GLOSSY = 2, YK_MAT_COATED_GLOSSY = 4 };
 typedef struct yk_material {
   int32_t type;           /* YK_MAT_*                                               */
   float color[3];         /* "color"  shinydiffuse.cc:474,483 / simple.cc:82        */
@@ -79,6 +81,14 @@ typedef struct yk_material {
   int32_t as_diffuse;     /* "as_diffuse" [1]                                       */
   int32_t anisotropic;    /* "anisotropic" [0]: exp_u / exp_v instead of exponent   */
   float exp_u, exp_v;     /* "exp_u" [50], "exp_v" [50]                             */
+  /* coated_glossy (coatedGlossyMat_t::factory, coatedglossy.cc:420-498) adds no
+   * field: YK_MAT_COATED_GLOSSY reads the glossy fields as above plus
+   * `mirror_color` ("mirror_color" [1,1,1]) and `ior` ("IOR" [1.4 for this
+   * kind]). A zero-initialised struct must set IOR 1.4, mirror_color 1,
+   * exponent 50, glossy_reflect 1, diffuse_reflect 0, as_diffuse 1. The
+   * factory's `if(ior == 1.f) ior = 1.0000001f` is applied as written (the
+   * double compared with and assigned a float literal, then held as a float).
+   * as_diffuse == 0 is YK_ERR_UNSUPPORTED here too. */
 } yk_material;
 enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 
@@ -339,11 +349,14 @@ const char* yk_version(void);
 /* ---- host scene (scene_t geometry state machine + update) ---- */
 int yk_scene_create(yk_scene** out);
 void yk_scene_destroy(yk_scene* s);
-/* YK_ERR_UNSUPPORTED for an unknown type and for a glossy material with
- * as_diffuse == 0; YK_ERR_ARG for a glossy material with a non-finite colour,
- * glossy_reflect, diffuse_reflect or exponent (yk_scene_add_material_state
- * likewise, for the state's members, and for a glossy state whose bsdf_flags
- * are not exactly BSDF_DIFFUSE | BSDF_REFLECT) */
+/* YK_ERR_UNSUPPORTED for an unknown type and for a glossy or coated glossy
+ * material with as_diffuse == 0; YK_ERR_ARG for a glossy or coated glossy
+ * material with a non-finite colour, glossy_reflect, diffuse_reflect or
+ * exponent (a coated one: mirror_color and ior too).
+ * yk_scene_add_material_state likewise, for the state's members; for a glossy
+ * state whose bsdf_flags are not exactly BSDF_DIFFUSE | BSDF_REFLECT; and for
+ * a coated state whose bsdf_flags, ncomp and comp_flags are not what
+ * coatedglossy.cc:84-101 computes (see yk_material_state). */
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out);
 /* one TRIM mesh: points xyz (npoints*3), faces abc (nfaces*3); startTriMesh +
  * addVertex* + addTriangle* + endTriMesh (scene.cc:265-320,520-625) */
@@ -472,6 +485,14 @@ typedef struct yk_material_state {
   float reflectivity;       /* "glossy_reflect": MDat_t::mGlossy without shader nodes     */
   float m_diffuse;          /* mDiffuse                                                  */
   int32_t as_diffuse, with_diffuse, anisotropic;
+  /* coatedGlossyMat_t (coatedglossy.cc:63-77), appended: the member IOR; zero
+   * for the other kinds. A YK_MAT_COATED_GLOSSY state holds glossyMat_t's
+   * members above with the same meaning, mirror_color, and the constructor's
+   * flags (coatedglossy.cc:84-101): bsdf_flags = BSDF_SPECULAR | BSDF_REFLECT |
+   * BSDF_DIFFUSE, ncomp = nBSDF (3 with a diffuse base, else 2), comp_flags =
+   * cFlags {SPECULAR|REFLECT, DIFFUSE|REFLECT, DIFFUSE|REFLECT or BSDF_NONE};
+   * anything else is YK_ERR_ARG. */
+  float ior;
 } yk_material_state;
 
 typedef struct yk_area_light_state { /* areaLight_t members (arealight.h:45-53) */

@@ -1,5 +1,5 @@
 """Throughput of a Cornell-like room with glossy walls, path traced:
-  python tools/glossy_bench.py [--res 1024] [--spp 64] [--steps 3] [--warmup 1]
+  python tools/glossy_bench.py [--res 1024] [--spp 64] [--steps 3] [--warmup 1] [--coated]
 The room is closed (floor, ceiling, three walls, the camera looks in through
 the open fourth side) with one box and one area light under the ceiling. It is
 rendered twice: every surface glossy (isotropic and anisotropic lobes over a
@@ -7,7 +7,10 @@ diffuse base, one with Oren-Nayar), then every surface shinydiffuse with the
 same diffuse part, so the glossy instantiations' cost stands beside the
 diffuse-only kernels' on the same geometry. One JSON line per form: Mrays/s
 (closest + shadow rays over wall time, film resolve included, as bench.py
-counts them). Ungated: a record, not a check."""
+counts them). --coated renders a third form first: the same room with every
+glossy surface coated (coated_glossy, IOR 1.4, white mirror_color) and
+raydepth 2, so the coat's recursion rays are in the count. Ungated: a record,
+not a check."""
 import argparse
 import ctypes as C
 import json
@@ -35,9 +38,14 @@ LOBES = [dict(exponent=500.0), dict(exponent=50.0), dict(anisotropic=True, exp_u
          dict(exponent=50.0)]
 
 
-def room(res, glossy):
+def room(res, form):
     s = Scene()
-    if glossy:
+    glossy = form == "glossy"
+    if form == "coated":
+        m = [s.add_material(type_=A.YK_MAT_COATED_GLOSSY, color=(0.9, 0.85, 0.8), glossy_reflect=0.3, diffuse_color=c,
+                            diffuse_reflect=d, ior=1.4, mirror_color=(1, 1, 1), **lobe)
+             for (c, d), lobe in zip(DIFFUSE, LOBES)]
+    elif glossy:
         m = [s.add_material(type_=A.YK_MAT_GLOSSY, color=(0.9, 0.85, 0.8), glossy_reflect=0.3, diffuse_color=c,
                             diffuse_reflect=d, **lobe) for (c, d), lobe in zip(DIFFUSE, LOBES)]
     else:
@@ -61,6 +69,7 @@ def main():
     ap.add_argument("--spp", type=int, default=64)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--coated", action="store_true", help="also the room with every glossy surface coated")
     a = ap.parse_args()
     p = A.yk_render_params()
     A.lib().yk_render_params_default(C.byref(p))
@@ -71,8 +80,10 @@ def main():
     p.path_samples = 1
     p.bounces = 4
     dev = Device(0)
-    for form in ("glossy", "shinydiffuse"):
-        dev.upload(room(a.res, form == "glossy"))
+    for form in (("coated",) if a.coated else ()) + ("glossy", "shinydiffuse"):
+        if form == "coated":
+            p.raydepth = 2  # the other forms hold no specular material: raydepth does not reach them
+        dev.upload(room(a.res, form))
         film = dev.new_film(p)
 
         def step(st):

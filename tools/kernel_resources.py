@@ -7,7 +7,9 @@ flags. No GPU is needed.
   tools/kernel_resources.py diff OLD NEW      compare two saved tables
 
 Kernel names are demangled, and the trailing template argument GL (the scene
-holds a glossy material) is dropped where it is `false`, its default: the
+holds a glossy material; since the coated glossy material a level: 0 none,
+1 glossy, 2 coated glossy, where 1 is listed as `true`, the flag's earlier
+spelling) is dropped where it is `false` or 0, its default: the
 table lists k_shade_primary<false, 0, false, false> as
 k_shade_primary<false, 0, false> and k_photon_hit<false> as k_photon_hit, so
 tables from before and after a kernel gained the argument line up.
@@ -25,7 +27,7 @@ FIELDS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy
           "VGPRs Spill", "LDS Size [bytes/block]"]
 # template arity, GL included, of the kernels whose last template argument is GL
 GL_ARITY = {"k_shade_primary": 4, "k_shade_bounce": 3, "k_path_start": 2, "k_fg_start": 2, "k_fg_hit": 2,
-            "k_photon_hit": 1, "k_pm_post": 1, "k_pm_finish": 1, "k_pt_caustic": 1}
+            "k_photon_hit": 1, "k_pm_post": 1, "k_pm_finish": 1, "k_pt_caustic": 1, "k_spawn": 1}
 
 
 def short_name(mangled):
@@ -35,8 +37,11 @@ def short_name(mangled):
     m = re.match(r"(\w+)<(.*)>$", name)
     if m and m.group(1) in GL_ARITY:
         args = [a.strip() for a in m.group(2).split(",")]
-        if len(args) == GL_ARITY[m.group(1)] and args[-1] == "false":
+        # GL became a level (0 none, 1 glossy, 2 coated glossy): 0 and 1 print as the flag's false and true did
+        if len(args) == GL_ARITY[m.group(1)] and args[-1] in ("false", "0"):
             name = f"{m.group(1)}<{', '.join(args[:-1])}>" if len(args) > 1 else m.group(1)
+        elif len(args) == GL_ARITY[m.group(1)] and args[-1] == "1":
+            name = f"{m.group(1)}<{', '.join(args[:-1] + ['true'])}>"
     return name
 
 
