@@ -36,6 +36,7 @@
 #include "../../include/yk_test_hooks_film.h"
 #include "../../include/yk_test_hooks_depth.h"
 #include "../../include/yk_test_hooks_material.h"
+#include "../../include/yk_test_hooks_photon.h"
 #include "photon_map.h"
 #include "scene.h"
 #include "yk_internal.h"

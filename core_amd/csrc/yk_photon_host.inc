@@ -6,6 +6,10 @@
 
 namespace {
 
+// deepest point kd-tree the device lookups take: a lookup pushes one stack
+// entry per interior level, and the stacks hold kPStack
+constexpr int kMaxPointTreeDepth = kPStack - 2;
+
 // light_t::totalEnergy().energy(): areaLight_t color * area (arealight.cc:66),
 // pointLight_t color * 4.0f * M_PI (pointlight.cc:32), directionalLight_t
 // color * radius*radius * M_PI (directional.cc:33); energy() = (R+G+B)*0.333333f
@@ -268,7 +272,7 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
   PointTree dtree;
   if (!pt) {
     point_tree_build(dm.data(), 9, ndm, dtree);
-    if (dtree.depth > kPStack - 2) return set_error(YK_ERR_UNSUPPORTED, "diffuse photon tree too deep");
+    if (dtree.depth > kMaxPointTreeDepth) return set_error(YK_ERR_UNSUPPORTED, "diffuse photon tree too deep");
     upload_map(d, YK_PHOTON_MAP_DIFFUSE, dm, dtree);
   }
   // caustic map, same push order
@@ -287,7 +291,7 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
   if (!cm.empty()) {
     PointTree ctree;
     point_tree_build(cm.data(), 9, (int)(cm.size() / 9), ctree);
-    if (ctree.depth > kPStack - 2) return set_error(YK_ERR_UNSUPPORTED, "caustic photon tree too deep");
+    if (ctree.depth > kMaxPointTreeDepth) return set_error(YK_ERR_UNSUPPORTED, "caustic photon tree too deep");
     cdepth = ctree.depth;
     upload_map(d, YK_PHOTON_MAP_CAUSTIC, cm, ctree);
   }
@@ -350,7 +354,7 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
     }
     PointTree rtree;
     point_tree_build(rm.data(), 9, nr, rtree);
-    if (rtree.depth > kPStack - 2) return set_error(YK_ERR_UNSUPPORTED, "radiance photon tree too deep");
+    if (rtree.depth > kMaxPointTreeDepth) return set_error(YK_ERR_UNSUPPORTED, "radiance photon tree too deep");
     rdepth = rtree.depth;
     d->rm_depth = rtree.depth;
     d->rm_nnodes = rtree.nodes.size() / 2;

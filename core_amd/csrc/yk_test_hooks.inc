@@ -507,3 +507,314 @@ extern "C" int yk_debug_aa_flags(yk_device* d, const float* film, int32_t w, int
   return YK_OK;
   YK_GUARD_END
 }
+
+// ---------------------------------------------------------------------------
+// include/yk_test_hooks_photon.h: the photon-map lookups on a synthetic map.
+// yk_debug_photon_load takes yk_photon_build's steps from the kd-tree build
+// on; the probe kernels call pm_gather / pm_nearest, the functions k_pregather,
+// k_pm_post and caustic_estimate call; yk_debug_photon_lookup_queue launches
+// the production k_pm_lookup the way enqueue_photon_mapping does.
+
+namespace {
+
+__global__ void __launch_bounds__(64) k_photon_gather_probe(PMapDev M, const float* __restrict__ pos,
+                                                            const float* __restrict__ r2, long long nq, int K,
+                                                            int* __restrict__ count, int* __restrict__ idx,
+                                                            float* __restrict__ d2, float* __restrict__ r2_out) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  PFound f[kMaxSearch];
+  const v3 p = V3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+  float radius = r2[i];
+  const int ng = M.n > 0 ? pm_gather(M, p, f, K, radius) : 0;  // the guard of k_pm_post / k_pm_finish
+  count[i] = ng;
+  r2_out[i] = radius;
+  for (int k = 0; k < ng; ++k) {
+    idx[i * K + k] = f[k].idx;
+    d2[i * K + k] = f[k].d2;
+  }
+}
+
+__global__ void __launch_bounds__(64) k_photon_nearest_probe(PMapDev M, const float* __restrict__ pos,
+                                                             const float* __restrict__ nrm,
+                                                             const float* __restrict__ r2, long long nq,
+                                                             int* __restrict__ nearest) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const v3 p = V3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
+  const v3 n = V3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]);
+  nearest[i] = M.n > 0 ? pm_nearest(M, p, n, r2[i]) : -1;
+}
+
+bool photon_slot_ok(int32_t which) {
+  return which == YK_PHOTON_MAP_DIFFUSE || which == YK_PHOTON_MAP_CAUSTIC || which == YK_PHOTON_MAP_RADIANCE;
+}
+
+// the PMapDev pm_const hands the render kernels for this slot
+PMapDev debug_map(const yk_device* d, int32_t which) {
+  if (which == YK_PHOTON_MAP_RADIANCE)
+    return PMapDev{d->rm_nodes.p, d->rm_pos.p, d->rm_dir.p, d->rm_col.p, (int)(d->rm_host.size() / 9), d->rm_pk.p};
+  if (which == YK_PHOTON_MAP_CAUSTIC)
+    return PMapDev{d->cm_nodes.p, d->cm_pos.p, d->cm_dir.p, d->cm_col.p, (int)(d->cm_host.size() / 9)};
+  return PMapDev{d->dm_nodes.p, d->dm_pos.p, d->dm_dir.p, d->dm_col.p, (int)(d->dm_host.size() / 9)};
+}
+
+constexpr int64_t kProbeMaxQueries = 1ll << 24;
+constexpr int64_t kProbeMaxRecords = 1ll << 26;  // nq * K of one gather call
+constexpr int64_t kProbeMaxQueue = 1ll << 25;
+
+// photonGather_t::operator() (photon.cc:53-73) over libstdc++'s own heap functions
+struct HostFound {
+  int idx;
+  float d2;
+  bool operator<(const HostFound& o) const { return d2 < o.d2; }
+};
+struct HostGather {
+  HostFound* f;
+  int k, n;
+  void operator()(int d, float dist2, float& maxd2) {
+    if (n < k) {
+      f[n++] = HostFound{d, dist2};
+      if (n == k) {
+        std::make_heap(f, f + k);
+        maxd2 = f[0].d2;
+      }
+    } else {
+      std::pop_heap(f, f + k);
+      f[k - 1] = HostFound{d, dist2};
+      std::push_heap(f, f + k);
+      maxd2 = f[0].d2;
+    }
+  }
+};
+// nearestPhoton_t::operator(), photon.h:167-176
+struct HostNearest {
+  const float* photons;
+  const float* n;
+  int nearest;
+  void operator()(int d, float dist2, float& maxd2) {
+    const float* w = photons + 9 * (size_t)d + 3;
+    if (w[0] * n[0] + w[1] * n[1] + w[2] * n[2] > 0.f) {
+      nearest = d;
+      maxd2 = dist2;
+    }
+  }
+};
+
+}  // namespace
+
+extern "C" int yk_debug_photon_load(yk_device* d, int32_t which, const float* photons, int32_t n, int32_t depth_limit,
+                                    yk_photon_map_info* info) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_load: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !photon_slot_ok(which) || n < 0 || n > (1 << 24) || (n > 0 && !photons))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_load: bad arguments");
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  std::vector<float> ph(photons, photons + 9 * (size_t)n);
+  PointTree t;
+  point_tree_build(ph.data(), 9, n, t);
+  const int limit = (depth_limit > 0 && depth_limit < kMaxPointTreeDepth) ? depth_limit : kMaxPointTreeDepth;
+  if (t.depth > limit) return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_load: photon tree too deep");
+  HIPCHK(hipStreamSynchronize(d->stream));
+  d->pm_ready = false;  // the slots no longer hold what pm_params describes
+  const bool radiance = which == YK_PHOTON_MAP_RADIANCE;
+  std::vector<float>& host = radiance ? d->rm_host : (which == YK_PHOTON_MAP_CAUSTIC ? d->cm_host : d->dm_host);
+  host.swap(ph);
+  if (radiance) {
+    d->rm_depth = t.depth;
+    d->rm_nnodes = t.nodes.size() / 2;
+  }
+  upload_map(d, which, host, t);
+  if (radiance && lookup_lds(d)) {
+    int blocks = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_pm_lookup<true>, 64, lookup_lds_bytes(d->rm_depth)));
+    d->per_cu_lookup[1] = std::max(1, blocks);
+  }
+  if (info) {
+    *info = yk_photon_map_info{};
+    info->photons = n;
+    info->nodes = (int32_t)(t.nodes.size() / 2);
+    info->depth = t.depth;
+    if (radiance) {
+      const bool lds = lookup_lds(d);
+      info->lookup_lds = lds ? 1 : 0;
+      info->lookup_grid = (int32_t)((long long)d->cus * d->per_cu_lookup[lds]);
+    }
+  }
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_gather(yk_device* d, int32_t which, const float* pos, const float* r2, int64_t nq,
+                                      int32_t K, int32_t* count, int32_t* idx, float* d2, float* r2_out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_gather: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !photon_slot_ok(which) || nq < 0 || nq > kProbeMaxQueries ||
+      (nq > 0 && (!pos || !r2 || !count || !idx || !d2 || !r2_out)))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_gather: bad arguments");
+  if (K < 1 || K > kMaxSearch) return set_error(YK_ERR_UNSUPPORTED, "search must be in [1, 256]");
+  if (nq * K > kProbeMaxRecords) return set_error(YK_ERR_ARG, "yk_debug_photon_gather: too many records");
+  if (nq == 0) return YK_OK;
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  const size_t n = (size_t)nq, nk = n * (size_t)K;
+  DBuf<float> dpos, dr2, dd2, dr2o;
+  DBuf<int> dcnt, didx;
+  dpos.ensure(3 * n);
+  dr2.ensure(n);
+  dr2o.ensure(n);
+  dcnt.ensure(n);
+  didx.ensure(nk);
+  dd2.ensure(nk);
+  HIPCHK(hipMemcpy(dpos.p, pos, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dr2.p, r2, n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(didx.p, 0xFF, nk * sizeof(int), d->stream));
+  HIPCHK(hipMemsetAsync(dd2.p, 0xFF, nk * sizeof(float), d->stream));
+  launch(k_photon_gather_probe, grid_for(nq, 64), 64, 0, d->stream, debug_map(d, which), (const float*)dpos.p,
+         (const float*)dr2.p, (long long)nq, (int)K, dcnt.p, didx.p, dd2.p, dr2o.p);
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(count, dcnt.p, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(idx, didx.p, nk * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(d2, dd2.p, nk * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(r2_out, dr2o.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_nearest(yk_device* d, int32_t which, const float* pos, const float* nrm,
+                                       const float* r2, int64_t nq, int32_t* nearest) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_nearest: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || !photon_slot_ok(which) || nq < 0 || nq > kProbeMaxQueries || (nq > 0 && (!pos || !nrm || !r2 || !nearest)))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_nearest: bad arguments");
+  if (nq == 0) return YK_OK;
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  const size_t n = (size_t)nq;
+  DBuf<float> dpos, dnrm, dr2;
+  DBuf<int> dout;
+  dpos.ensure(3 * n);
+  dnrm.ensure(3 * n);
+  dr2.ensure(n);
+  dout.ensure(n);
+  HIPCHK(hipMemcpy(dpos.p, pos, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dnrm.p, nrm, 3 * n * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dr2.p, r2, n * sizeof(float), hipMemcpyHostToDevice));
+  launch(k_photon_nearest_probe, grid_for(nq, 64), 64, 0, d->stream, debug_map(d, which), (const float*)dpos.p,
+         (const float*)dnrm.p, (const float*)dr2.p, (long long)nq, dout.p);
+  HIPCHK(hipStreamSynchronize(d->stream));
+  HIPCHK(hipMemcpy(nearest, dout.p, n * sizeof(int), hipMemcpyDeviceToHost));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_lookup_queue(yk_device* d, const float* lq, int64_t nq, float rad2,
+                                            int32_t force_scratch, float* lcol, int64_t ncol, int32_t* lds_out,
+                                            int32_t* grid_out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_lookup_queue: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (!d || nq < 0 || nq > kProbeMaxQueue || ncol < 0 || ncol > 3 * kProbeMaxQueue || (nq > 0 && !lq) ||
+      (ncol > 0 && !lcol))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_lookup_queue: bad arguments");
+  if (d->rm_host.empty() || d->rm_nnodes == 0)
+    return set_error(YK_ERR_STATE, "yk_debug_photon_lookup_queue: the radiance slot is empty");
+  for (int64_t q = 0; q < nq; ++q) {  // k_pm_lookup writes lcol[3 * owner .. + 2] unchecked
+    int32_t owner;
+    std::memcpy(&owner, &lq[8 * q + 3], sizeof owner);
+    if (owner < 0 || 3 * (int64_t)owner + 2 >= ncol)
+      return set_error(YK_ERR_ARG, "yk_debug_photon_lookup_queue: an owner outside the colour array");
+  }
+  YK_GUARD_BEGIN
+  HIPCHK(hipSetDevice(d->ordinal));
+  DBuf<float4> dlq;
+  DBuf<float> dcol;
+  DBuf<unsigned long long> words;  // [0] the queue's count word, [1] the hand-out's work word
+  dlq.ensure(std::max<size_t>(1, 2 * (size_t)nq));
+  dcol.ensure(std::max<size_t>(1, (size_t)ncol));
+  words.ensure(2);
+  const unsigned long long w[2] = {(unsigned long long)nq, 0ull};
+  if (nq > 0) HIPCHK(hipMemcpy(dlq.p, lq, (size_t)nq * 8 * sizeof(float), hipMemcpyHostToDevice));
+  if (ncol > 0) HIPCHK(hipMemcpy(dcol.p, lcol, (size_t)ncol * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(words.p, w, sizeof w, hipMemcpyHostToDevice));
+  const PMapDev rmap = debug_map(d, YK_PHOTON_MAP_RADIANCE);
+  const bool lds = !force_scratch && lookup_lds(d);
+  const unsigned grid = (unsigned)((long long)d->cus * d->per_cu_lookup[lds]);
+  launch(lds ? k_pm_lookup<true> : k_pm_lookup<false>, grid, 64, lds ? lookup_lds_bytes(d->rm_depth) : 0, d->stream,
+         rmap, rad2, d->rm_depth, (const float4*)dlq.p, (const unsigned long long*)words.p, dcol.p, words.p + 1);
+  HIPCHK(hipStreamSynchronize(d->stream));
+  if (ncol > 0) HIPCHK(hipMemcpy(lcol, dcol.p, (size_t)ncol * sizeof(float), hipMemcpyDeviceToHost));
+  if (lds_out) *lds_out = lds ? 1 : 0;
+  if (grid_out) *grid_out = (int32_t)grid;
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_host_tree(const float* photons, int32_t n, uint32_t* nodes, int64_t cap_nodes,
+                                         int32_t* nnodes, int32_t* depth) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_tree: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || cap_nodes < 0 || (cap_nodes > 0 && !nodes) || !nnodes || !depth)
+    return set_error(YK_ERR_ARG, "yk_debug_photon_host_tree: bad arguments");
+  YK_GUARD_BEGIN
+  PointTree t;
+  point_tree_build(photons, 9, n, t);
+  const size_t nn = t.nodes.size() / 2;
+  *nnodes = (int32_t)nn;
+  *depth = t.depth;
+  const size_t take = std::min<size_t>(nn, (size_t)cap_nodes);
+  if (take) std::memcpy(nodes, t.nodes.data(), take * 2 * sizeof(uint32_t));
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_host_gather(const float* photons, int32_t n, const float* pos, const float* r2,
+                                           int64_t nq, int32_t K, int32_t* count, int32_t* idx, float* d2,
+                                           float* r2_out) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_gather: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || nq < 0 || nq > kProbeMaxQueries ||
+      (nq > 0 && (!pos || !r2 || !count || !idx || !d2 || !r2_out)))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_host_gather: bad arguments");
+  if (K < 1 || K > kMaxSearch) return set_error(YK_ERR_UNSUPPORTED, "search must be in [1, 256]");
+  YK_GUARD_BEGIN
+  PointTree t;
+  point_tree_build(photons, 9, n, t);
+  if (t.depth > kMaxPointTreeDepth) return set_error(YK_ERR_UNSUPPORTED, "photon tree too deep");
+  std::vector<HostFound> f((size_t)K);
+  for (int64_t q = 0; q < nq; ++q) {
+    HostGather g{f.data(), K, 0};
+    float radius = r2[q];
+    if (n > 0) point_tree_lookup(t, photons, 9, pos + 3 * q, g, radius);
+    count[q] = g.n;
+    r2_out[q] = radius;
+    for (int k = 0; k < K; ++k) {
+      idx[q * K + k] = k < g.n ? f[k].idx : -1;
+      if (k < g.n) d2[q * K + k] = f[k].d2;
+      else std::memset(&d2[q * K + k], 0xFF, sizeof(float));
+    }
+  }
+  return YK_OK;
+  YK_GUARD_END
+}
+
+extern "C" int yk_debug_photon_host_nearest(const float* photons, int32_t n, const float* pos, const float* nrm,
+                                            const float* r2, int64_t nq, int32_t* nearest) {
+  if (!debug_hooks_on())
+    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_nearest: test hook disabled (YK_DEBUG_HOOKS=1)");
+  if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || nq < 0 || nq > kProbeMaxQueries ||
+      (nq > 0 && (!pos || !nrm || !r2 || !nearest)))
+    return set_error(YK_ERR_ARG, "yk_debug_photon_host_nearest: bad arguments");
+  YK_GUARD_BEGIN
+  PointTree t;
+  point_tree_build(photons, 9, n, t);
+  if (t.depth > kMaxPointTreeDepth) return set_error(YK_ERR_UNSUPPORTED, "photon tree too deep");
+  for (int64_t q = 0; q < nq; ++q) {
+    HostNearest pr{photons, nrm + 3 * q, -1};
+    float radius = r2[q];
+    if (n > 0) point_tree_lookup(t, photons, 9, pos + 3 * q, pr, radius);
+    nearest[q] = pr.nearest;
+  }
+  return YK_OK;
+  YK_GUARD_END
+}
