@@ -2360,15 +2360,15 @@ __device__ __forceinline__ void coated_specular(const DMat& M, const SurfPt& sp,
 // (y + z) + x; mD = ((1-c2)*c3)*mT), then mD *= OrenNayar(wo, wl, N) (:247).
 // ON = false: the scene has no Oren-Nayar material (the diffuse-only
 // instantiation's scenes), so the factor's code is not compiled in.
-// GL = true: the scene holds a glossy material; only then is glossy's code
+// GL != kGLNone: the scene holds a glossy material; only then is glossy's code
 // compiled in (mat_sample and mat_pdf likewise), so every other scene runs
 // the kernels it ran before. bsdfs is BSDF_ALL at every call site.
-// GL is a level: kGLNone, kGLGlossy (true in the instantiations' names), or
+// GL is a level: kGLNone, kGLGlossy (1 in the instantiations' names), or
 // kGLCoated when the scene holds a coated glossy material as well or instead;
 // only then is the coat's code compiled in, so glossy-only scenes too run the
 // kernels they ran before.
 constexpr int kGLNone = 0, kGLGlossy = 1, kGLCoated = 2;
-template <bool ON = true, int GL = false>
+template <bool ON = true, int GL = kGLNone>
 __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wl) {
   if (M.type == YK_MAT_LIGHT) return C3(0.f, 0.f, 0.f);
   if constexpr (GL) {
@@ -2402,7 +2402,7 @@ __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v
 // same float operations on the same values -- sum = 0 + w, the normalisation
 // by 1/sum, s1 / wp -- without the loop's per-lane arrays (the shading
 // kernels' registers).
-template <bool DIFF = false, int GL = false>
+template <bool DIFF = false, int GL = kGLNone>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok, unsigned& sflags) {
   static_assert(!(DIFF && GL), "a scene with a glossy material is never diffuse-only");
@@ -2518,7 +2518,7 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
   W = fabsf(vdot(w, sp.N)) / (pdf * 0.99f + 0.01f);
   return sc;
 }
-template <bool DIFF = false, int GL = false>
+template <bool DIFF = false, int GL = kGLNone>
 __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1in, float s2in,
                                          unsigned flags, float& pdf, float& W, bool& ok) {
   unsigned sf;
@@ -2529,7 +2529,7 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
 // bit with bsdfs adds its width to the sum; only diffuse ones add pdf.
 // Called with bsdfs = GLOSSY|DIFFUSE|DISPERSIVE|REFLECT|TRANSMIT, which
 // overlaps every shinydiffuse component.
-template <int GL = false>
+template <int GL = kGLNone>
 __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo, v3 wi) {
   if (M.type == YK_MAT_LIGHT) return 0.f;
   if constexpr (GL) {
@@ -2565,7 +2565,7 @@ __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo,
 // grazing correction in double). GL: the scene holds a glossy or coated glossy
 // material; a coated one answers with its own getSpecular at recursion level
 // raylevel, and its record is never read through the shinydiffuse members.
-template <int GL = false>
+template <int GL = kGLNone>
 __device__ __forceinline__ void mat_specular(const DMat& M, const SurfPt& sp, v3 wo, bool& refl, bool& refr,
                                              v3* dir, c3* col, int raylevel = 0) {
   refl = refr = false;
@@ -3515,7 +3515,7 @@ __device__ __forceinline__ bool light_sampled(const DLight& L) {
   return L.type == YK_LIGHT_AREA || L.type == YK_LIGHT_SPHERE || L.type == YK_LIGHT_MESH || L.soft != 0;
 }
 
-template <bool DIFF, int KIND, int GL = false>
+template <bool DIFF, int KIND, int GL = kGLNone>
 __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, const DLight& L, const DMat& M,
                                            const SurfPt& sp, v3 wo, unsigned pixelSample, unsigned soffs,
                                            unsigned loffs, unsigned long long& traced,
@@ -3526,9 +3526,9 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
 // slot with the contribution it adds when unoccluded. Returns #rays; sets bit
 // k of `traced` (k < 64) for each slot that holds a ray.
 // XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light) or
-// kXLMesh (it holds a mesh light; ml = DScene::ml): see shade_primary_fn
+// kXLMesh (it holds a mesh light; ml = DScene::ml): see kShade
 constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2;
-template <bool DIFF = false, int XL = kXLNone, int GL = false>
+template <bool DIFF = false, int XL = kXLNone, int GL = kGLNone>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
                                          unsigned long long& traced, const DMat* mats = c_mats,
@@ -3699,7 +3699,7 @@ constexpr unsigned kAOFlags = BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_REFLECT;
 // returns early (no component matches, or their widths sum below 1e-5) leaves
 // W = 0 and the previous direction: its term is +0 whatever the ray meets,
 // and the slot traces nothing.
-template <bool DIFF, int GL = false>
+template <bool DIFF, int GL = kGLNone>
 __device__ __forceinline__ int gen_ao(const Batch& B, long long c, const AOConst& A, const DMat& M, const SurfPt& sp,
                                       v3 wo, unsigned pixelSample, unsigned soffs, unsigned long long& traced) {
   const c3 black = C3(0.f, 0.f, 0.f);
@@ -3748,7 +3748,7 @@ __device__ __forceinline__ void flush_shadow(const Batch& B, long long c, int ke
 
 // First segment of sub-path isub from a diffuse camera-ray hit: sample the
 // primary BSDF (pathtracer.cc:169-187). Returns the segment's ray.
-template <bool DIFF = false, int GL = false>
+template <bool DIFF = false, int GL = kGLNone>
 __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const RenderConst& R, long long c,
                                                      const SurfPt& sp, const DMat& M, v3 dir, int isub) {
   const unsigned s = R.ps ? B.psample[c] : (unsigned)c % (unsigned)R.spp;
@@ -3782,7 +3782,7 @@ __device__ __forceinline__ yk_ray path_first_segment(const Batch& B, const Rende
 // AO: direct lighting with ambient occlusion (gen_ao) -- an instantiation of
 // its own, so the others carry none of its code; A is read by it alone.
 // GL: the scene holds a glossy material (mat_eval); DIFF is false then.
-template <bool DIFF, int XL, bool AO, int GL = false>
+template <bool DIFF, int XL, bool AO, int GL = kGLNone>
 __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Batch B, RenderConst R, long long nc,
                                                        unsigned long long* __restrict__ qword, AOConst A) {
   // The material records in LDS: per-lane reads of constant memory (the
@@ -4012,7 +4012,7 @@ __global__ void __launch_bounds__(256) k_resolve_ao(DScene S, Batch B, RenderCon
 
 // First segment of sub-paths isub >= 1 (sub-path 0 is fused into
 // k_shade_primary).
-template <bool DIFF, int GL = false>
+template <bool DIFF, int GL = kGLNone>
 __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch B, RenderConst R, long long nc, int isub,
                                                     unsigned long long* __restrict__ qword) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -4043,7 +4043,7 @@ __global__ void __launch_bounds__(YK_BOUNCE_BLOCK) k_path_start(DScene S, Batch 
 // (pathtracer.cc:189-298): estimateOneDirectLight shadow rays, emission,
 // and the BSDF sample of the next segment. One thread per live path (entry
 // qi of the input bounce queue, owned by camera sample c).
-template <bool DIFF, int XL, int GL = false>
+template <bool DIFF, int XL, int GL = kGLNone>
 __global__ void __launch_bounds__(bounce_block(DIFF))
 __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES))) k_shade_bounce(DScene S, Batch B, RenderConst R,
                                                       const unsigned long long* __restrict__ qin_word, int depth,
@@ -4165,52 +4165,6 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
     st_ray(&B.q_rays[qin ^ 1][qn], nxt);
     B.q_owner[qin ^ 1][qn] = (int)c;
   }
-}
-
-// The shading kernels' instantiation: DIFF (diffuse-only materials) and XL
-// (the scene holds a spot or sphere light). With the spot and sphere code in
-// every instantiation k_shade_primary grew from 105 / 123 to 117 / 132 VGPRs
-// (the general one from 4 to 3 waves per SIMD) and k_shade_bounce, held at 96,
-// spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
-// therefore run kernels that leave that code out (XL = false), as scenes
-// with plain diffuse materials leave out the component loop.
-// A mesh light (kXLMesh) adds its own instantiations on top of the spot and
-// sphere code: meshLight_t::intersect walks the light's kd-tree per BSDF-half
-// sample with a per-lane stack in scratch memory (MeshStack), which no other
-// scene pays for.
-// A glossy material (GL) adds general-material instantiations of its own in
-// the same way, one per XL x AO: glossy's lobe code reaches no other scene.
-inline auto shade_primary_fn(bool diff, int xl, bool ao, int gl) {
-  if (gl == kGLCoated) {
-    if (xl == kXLMesh) return ao ? k_shade_primary<false, kXLMesh, true, kGLCoated> : k_shade_primary<false, kXLMesh, false, kGLCoated>;
-    if (xl) return ao ? k_shade_primary<false, kXLSpotSphere, true, kGLCoated> : k_shade_primary<false, kXLSpotSphere, false, kGLCoated>;
-    return ao ? k_shade_primary<false, kXLNone, true, kGLCoated> : k_shade_primary<false, kXLNone, false, kGLCoated>;
-  }
-  if (gl) {
-    if (xl == kXLMesh) return ao ? k_shade_primary<false, kXLMesh, true, true> : k_shade_primary<false, kXLMesh, false, true>;
-    if (xl) return ao ? k_shade_primary<false, kXLSpotSphere, true, true> : k_shade_primary<false, kXLSpotSphere, false, true>;
-    return ao ? k_shade_primary<false, kXLNone, true, true> : k_shade_primary<false, kXLNone, false, true>;
-  }
-  if (xl == kXLMesh) {
-    if (ao) return diff ? k_shade_primary<true, kXLMesh, true> : k_shade_primary<false, kXLMesh, true>;
-    return diff ? k_shade_primary<true, kXLMesh, false> : k_shade_primary<false, kXLMesh, false>;
-  }
-  if (ao)
-    return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, true> : k_shade_primary<false, kXLSpotSphere, true>)
-              : (diff ? k_shade_primary<true, kXLNone, true> : k_shade_primary<false, kXLNone, true>);
-  return xl ? (diff ? k_shade_primary<true, kXLSpotSphere, false> : k_shade_primary<false, kXLSpotSphere, false>)
-            : (diff ? k_shade_primary<true, kXLNone, false> : k_shade_primary<false, kXLNone, false>);
-}
-inline auto shade_bounce_fn(bool diff, int xl, int gl) {
-  if (gl == kGLCoated)
-    return xl == kXLMesh ? k_shade_bounce<false, kXLMesh, kGLCoated>
-                         : (xl ? k_shade_bounce<false, kXLSpotSphere, kGLCoated> : k_shade_bounce<false, kXLNone, kGLCoated>);
-  if (gl)
-    return xl == kXLMesh ? k_shade_bounce<false, kXLMesh, true>
-                         : (xl ? k_shade_bounce<false, kXLSpotSphere, true> : k_shade_bounce<false, kXLNone, true>);
-  if (xl == kXLMesh) return diff ? k_shade_bounce<true, kXLMesh> : k_shade_bounce<false, kXLMesh>;
-  return xl ? (diff ? k_shade_bounce<true, kXLSpotSphere> : k_shade_bounce<false, kXLSpotSphere>)
-            : (diff ? k_shade_bounce<true, kXLNone> : k_shade_bounce<false, kXLNone>);
 }
 
 // pathCol += lcol*throughput; throughput *= scol of the next segment. One
@@ -4398,7 +4352,7 @@ __global__ void __launch_bounds__(256) k_finish_spec(Batch B, RenderConst R, Nod
 // recursiveRaytrace's specular block for the hits of one chunk: allocate the
 // reflect / refract children (rays from sp.P, tmin MIN_RAYDIST, unbounded).
 // GL: as in the shading kernels (a coated glossy material's getSpecular).
-template <int GL = false>
+template <int GL = kGLNone>
 __global__ void __launch_bounds__(256) k_spawn(DScene S, Batch B, RenderConst R, NodeStore NS, long long base,
                                                long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -5290,6 +5244,68 @@ constexpr TraceInfo kTrace[kTraceVariants] = {
     {k_trace_camera_small, YK_SMALL_W, true, YK_SMALL_RING},
 };
 
+// The shading kernels of a scene, as a table. A scene's variant is its
+// material level (the kernels' DIFF and GL arguments, which exclude each
+// other: mat_sample) and its light level (XL), both fixed at upload.
+// kMatDiffuse: every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>);
+// kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated)
+enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kShadeMats };
+constexpr int kXLLevels = kXLMesh + 1;
+struct ShadeVariant {
+  int mat = kMatGeneral;  // ShadeMat
+  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light
+};
+struct ShadeKernels {
+  decltype(&k_shade_primary<false, kXLNone, false>) primary[2];  // [AO]
+  decltype(&k_shade_bounce<false, kXLNone>) bounce;
+  int bounce_block;
+  decltype(&k_path_start<false>) path_start;
+  decltype(&k_spawn<>) spawn;
+  decltype(&k_fg_start<false>) fg_start;
+  decltype(&k_fg_hit<false>) fg_hit;
+  decltype(&k_pm_post<>) pm_post;
+  decltype(&k_pm_finish<>) pm_finish;
+  decltype(&k_pt_caustic<>) pt_caustic;
+  decltype(&k_photon_hit<>) photon_hit;
+};
+// Which instantiation a variant runs: DIFF (diffuse-only materials) and XL
+// (the scene holds a spot or sphere light). With the spot and sphere code in
+// every instantiation k_shade_primary grew from 105 / 123 to 117 / 132 VGPRs
+// (the general one from 4 to 3 waves per SIMD) and k_shade_bounce, held at 96,
+// spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
+// therefore run kernels that leave that code out (kXLNone), as scenes
+// with plain diffuse materials leave out the component loop.
+// A mesh light (kXLMesh) adds its own instantiations on top of the spot and
+// sphere code: meshLight_t::intersect walks the light's kd-tree per BSDF-half
+// sample with a per-lane stack in scratch memory (MeshStack), which no other
+// scene pays for.
+// A glossy material (GL) adds general-material instantiations of its own in
+// the same way, one per XL x AO: glossy's lobe code reaches no other scene.
+// Only k_shade_primary and k_shade_bounce sample lights, so only they take XL;
+// the photon, k_pm_* and k_pt_caustic kernels take GL alone; k_spawn differs
+// only for the coat (mat_specular), so glossy scenes run the general one.
+template <int MAT, int XL>
+constexpr ShadeKernels shade_cell() {
+  constexpr bool DIFF = MAT == kMatDiffuse;
+  constexpr int GL = MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
+  return {{k_shade_primary<DIFF, XL, false, GL>, k_shade_primary<DIFF, XL, true, GL>}, k_shade_bounce<DIFF, XL, GL>,
+          bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL == kGLCoated ? kGLCoated : kGLNone)>,
+          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>, k_photon_hit<GL>};
+}
+constexpr ShadeKernels kShade[kShadeMats][kXLLevels] = {
+    {shade_cell<kMatDiffuse, kXLNone>(), shade_cell<kMatDiffuse, kXLSpotSphere>(), shade_cell<kMatDiffuse, kXLMesh>()},
+    {shade_cell<kMatGeneral, kXLNone>(), shade_cell<kMatGeneral, kXLSpotSphere>(), shade_cell<kMatGeneral, kXLMesh>()},
+    {shade_cell<kMatGlossy, kXLNone>(), shade_cell<kMatGlossy, kXLSpotSphere>(), shade_cell<kMatGlossy, kXLMesh>()},
+    {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>()},
+};
+// the table names no instantiation beyond today's: no glossy k_spawn, no DIFF or XL where a kernel takes none
+static_assert(kShade[kMatGlossy][kXLNone].spawn == kShade[kMatGeneral][kXLNone].spawn &&
+              kShade[kMatCoated][kXLNone].spawn != kShade[kMatGeneral][kXLNone].spawn &&
+              kShade[kMatDiffuse][kXLNone].photon_hit == kShade[kMatGeneral][kXLNone].photon_hit &&
+              kShade[kMatDiffuse][kXLNone].pm_post == kShade[kMatGeneral][kXLNone].pm_post &&
+              kShade[kMatCoated][kXLMesh].fg_hit == kShade[kMatCoated][kXLNone].fg_hit &&
+              kShade[kMatDiffuse][kXLMesh].path_start == kShade[kMatDiffuse][kXLNone].path_start);
+
 struct yk_device {
   int ordinal = 0;
   int cus = 0;
@@ -5314,14 +5330,12 @@ struct yk_device {
   DScene S{};
   int ntris = 0, max_depth = 0, nlights = 0, sum_light_slots = 0;
   bool spec = false;  // some material has SPECULAR|FILTER components: recursion pipeline
-  int xl_lights = 0;  // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light (shading kernels' XL instantiation)
+  ShadeVariant shade;  // material and light level of the scene: its shading kernels (shade_kernels)
   // mesh lights: one record per light in DScene::ml, its arrays packed in three buffers
   DBuf<DMeshLight> ml_recs;
   DBuf<float> ml_f;
   DBuf<uint2> ml_nodes;
   DBuf<uint32_t> ml_leaf;
-  bool diff_only = false;  // every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>)
-  int glossy = 0;          // kGLGlossy: a material is glossy; kGLCoated: one is coated glossy (the kernels' GL level)
   yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
   void* abort_user = nullptr;
   bool big_leaves = false;  // the resident tree has a leaf of 2^17 references or more: *_big kernels
@@ -5394,6 +5408,8 @@ struct yk_device {
 };
 
 namespace {
+inline const ShadeKernels& shade_kernels(const yk_device* d) { return kShade[d->shade.mat][d->shade.xl]; }
+
 // Constant memory (c_mats, c_lights, c_cam) is per GPU, not per handle: the
 // upload whose records a GPU's constants hold. Every yk_device_upload takes a
 // fresh process-wide token (the scene's generation alone is not enough: the
@@ -6198,17 +6214,15 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
     d->mat_flags.push_back(m.bsdf_flags);
     if (m.bsdf_flags & (BSDF_SPECULAR | BSDF_FILTER)) d->spec = true;
   }
-  {  // the shading kernels' diffuse-only instantiation (mat_sample<true>); YK_DIFF=0 never
+  {  // the scene's material level: the highest any material needs; YK_DIFF=0: never the diffuse-only one
     const char* e = std::getenv("YK_DIFF");
-    d->diff_only = !(e && std::atoi(e) == 0);
-    d->glossy = kGLNone;
+    int mat = (e && std::atoi(e) == 0) ? kMatGeneral : kMatDiffuse;
     for (const DMat& m : mats) {
-      const bool gl = m.type == YK_MAT_GLOSSY || m.type == YK_MAT_COATED_GLOSSY;
-      if (gl) d->glossy = std::max(d->glossy, m.type == YK_MAT_COATED_GLOSSY ? kGLCoated : kGLGlossy);  // never diffuse-only
-      if (gl ||
-          !(m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on)))
-        d->diff_only = false;
+      const bool diff = m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on);
+      mat = std::max<int>(mat, m.type == YK_MAT_COATED_GLOSSY ? kMatCoated : m.type == YK_MAT_GLOSSY ? kMatGlossy
+                               : diff ? kMatDiffuse : kMatGeneral);
     }
+    d->shade.mat = mat;
   }
   // mesh lights: check every light's tree before anything of them is resident
   // (a tree deeper than the shading kernels' per-lane stack is refused, not cut)
@@ -6281,12 +6295,12 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
     }
     sum_slots += lights.back().nslots;
   }
-  d->xl_lights = kXLNone;
+  d->shade.xl = kXLNone;
   for (const DLight& L : lights)
-    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) d->xl_lights = kXLSpotSphere;
+    if (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) d->shade.xl = kXLSpotSphere;
   d->S.ml = nullptr;
   if (!ml_recs.empty()) {
-    d->xl_lights = kXLMesh;
+    d->shade.xl = kXLMesh;
     d->ml_f.ensure(ml_f.size());
     d->ml_nodes.ensure(ml_nodes.size() / 2);
     d->ml_leaf.ensure(ml_leaf.size());

@@ -283,7 +283,7 @@ struct PhotonBuf {
 };
 
 // material_t::getReflectivity, material.cc:48-66
-template <int GL = false>
+template <int GL = kGLNone>
 __device__ __forceinline__ c3 get_reflectivity(const DMat& M, const SurfPt& sp, unsigned flags) {
   if (!(flags & (BSDF_TRANSMIT | BSDF_REFLECT) & M.flags)) return C3(0.f, 0.f, 0.f);
   float W = 0.f;
@@ -384,7 +384,7 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_emit(PhotonConst PC,
 // One hit of every live photon path (photonintegr.cc:256-314): deposit on a
 // diffuse surface, radiance-point data, and scatterPhoton for the next segment.
 // GL (here and below): the scene holds a glossy material, as in the shading kernels.
-template <int GL = false>
+template <int GL = kGLNone>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_hit(DScene S, PhotonConst PC, PhotonBuf PB, int bounce,
                                                     const unsigned long long* __restrict__ in_w, int qin,
                                                     unsigned long long* __restrict__ out_w) {
@@ -522,7 +522,7 @@ struct PMConst {
 // photonIntegrator_t::integrate after estimateAllDirectLight
 // (photonintegr.cc:819-866): show_map lookups and the direct diffuse-map
 // estimate of the non-final-gather mode.
-template <int GL = false>
+template <int GL = kGLNone>
 __global__ void __launch_bounds__(64) k_pm_post(DScene S, Batch B, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc) return;
@@ -567,7 +567,7 @@ enum : int { FG_ADD = 16, FG_EMIT = 32, FG_CAUS = 64, FG_SPECF = 128 };
 
 // "Zero'th" FG bounce of gather path isub (photonintegr.cc:660-684): sample
 // the camera hit's BSDF; a black weight skips the path.
-template <bool DIFF, int GL = false>
+template <bool DIFF, int GL = kGLNone>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B, RenderConst R, long long nc, int isub,
                                                   float* __restrict__ fg_lcol, unsigned long long* __restrict__ qword) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -619,7 +619,7 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B,
 #ifndef YK_FG_WAVES_D
 #define YK_FG_WAVES_D 1  // occupancy target of the diffuse-only k_fg_hit (1: the compiler's choice)
 #endif
-template <bool DIFF, int GL = false>
+template <bool DIFF, int GL = kGLNone>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(DIFF ? YK_FG_WAVES_D : 1)))
 k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
                                                 const unsigned long long* __restrict__ qin_word, int it, int isub,
@@ -899,7 +899,7 @@ __global__ void __launch_bounds__(256) k_fg_resolve(Batch B, RenderConst R,
 // mcIntegrator_t::estimateCausticPhotons (mcintegrator.cc:384-419, kernel()
 // sample_utils.h:27-31) at the hit of entry c; the caller checks
 // causticMap.ready() (cmap.n > 0).
-template <int GL = false>
+template <int GL = kGLNone>
 __device__ __forceinline__ c3 caustic_estimate(const DScene& S, const Batch& B, const PMConst& PM, long long c) {
   const yk_ray r = B.p_rays[c];
   const v3 from = V3(r.from[0], r.from[1], r.from[2]), dir = V3(r.dir[0], r.dir[1], r.dir[2]);
@@ -928,7 +928,7 @@ __device__ __forceinline__ c3 caustic_estimate(const DScene& S, const Batch& B, 
 
 // col += finalGathering (pathCol / nSampl) and col += estimateCausticPhotons
 // in the order photonIntegrator_t::integrate adds them (photonintegr.cc:827-852).
-template <int GL = false>
+template <int GL = kGLNone>
 __global__ void __launch_bounds__(64) k_pm_finish(DScene S, Batch B, RenderConst R, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc || !(B.prim_hit[c] & PH_DIFFUSE)) return;
@@ -946,7 +946,7 @@ __global__ void __launch_bounds__(64) k_pm_finish(DScene S, Batch B, RenderConst
 // pathIntegrator_t::integrate with caustic_type photon / both: col +=
 // estimateCausticPhotons right after estimateAllDirectLight on a diffuse hit
 // (pathtracer.cc:168-172), before the path samples are added.
-template <int GL = false>
+template <int GL = kGLNone>
 __global__ void __launch_bounds__(64) k_pt_caustic(DScene S, Batch B, PMConst PM, long long nc) {
   const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= nc || !(B.prim_hit[c] & PH_DIFFUSE)) return;

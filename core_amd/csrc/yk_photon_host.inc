@@ -201,8 +201,8 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
       unsigned long long* work = words.p + kAccWords + (MB + 2) + 128ll * b;
       enqueue_trace<true>(d, P, ray_src(PB.q_rays[qin]), nullptr, RayCount{qwd + b, 32, 0}, PB.q_hits[qin], nullptr, work,
                           words.p, nullptr, nullptr);
-      launch((d->glossy == kGLCoated ? k_photon_hit<kGLCoated> : d->glossy ? k_photon_hit<kGLGlossy> : k_photon_hit<kGLNone>), grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, d->S, C, PB, b, qwd + b, qin,
-             qwd + b + 1);
+      launch(shade_kernels(d).photon_hit, grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, d->S, C, PB, b, qwd + b,
+             qin, qwd + b + 1);
       qin ^= 1;
     }
     unsigned long long acc[kAccWords];

@@ -447,21 +447,22 @@ void enqueue_photon_mapping(BatchCtx& c, const Batch& Bc, const RenderConst& Rc,
   yk_device* d = c.d;
   Pipe& P = *c.P;
   const PMConst& PMC = c.fp->PMC;
+  const ShadeKernels& K = shade_kernels(d);
   const int fg_bounces = c.p->photon.fg_bounces;
-  if (PMC.show_map || !PMC.final_gather) launch((d->glossy == kGLCoated ? k_pm_post<kGLCoated> : d->glossy ? k_pm_post<kGLGlossy> : k_pm_post<kGLNone>), grid_for(n, 64), 64, 0, P.stream, d->S, Bc, PMC, n);
+  if (PMC.show_map || !PMC.final_gather) launch(K.pm_post, grid_for(n, 64), 64, 0, P.stream, d->S, Bc, PMC, n);
   // final gathering (photonintegr.cc:637-790): gather path index outermost,
   // pathCol accumulated across paths in the reference's order
   for (int isub = 0; isub < (Rc.pm_fg ? c.fp->nsub : 0); ++isub) {
-    launch(d->glossy == kGLCoated ? k_fg_start<false, kGLCoated> : d->glossy ? k_fg_start<false, kGLGlossy> : (d->diff_only ? k_fg_start<true> : k_fg_start<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
-           P.stream, d->S, Bc, Rc, n, isub, P.fgl.p, qw(c, isub, 0));
+    launch(K.fg_start, grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, d->S, Bc, Rc, n, isub, P.fgl.p,
+           qw(c, isub, 0));
     int qin = 1;
     for (int it = 0; it <= fg_bounces; ++it) {
       const unsigned long long* in_w = qw(c, isub, it);
       unsigned long long* out_w = qw(c, isub, it + 1);
       trace(c, true, ray_src(Bc.q_rays[qin]), nullptr, RayCount{in_w, 32, 0}, Bc.q_hits[qin], nullptr);
       unsigned long long* lk_w = qw(c, isub, it) + c.fp->qwords_per_batch;  // lookup-queue count
-      launch(d->glossy == kGLCoated ? k_fg_hit<false, kGLCoated> : d->glossy ? k_fg_hit<false, kGLGlossy> : (d->diff_only ? k_fg_hit<true> : k_fg_hit<false>), grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0,
-             P.stream, d->S, Bc, Rc, PMC, in_w, it, isub, qin, P.fgl.p, P.fglen.p, out_w, P.lkq.p, lk_w);
+      launch(K.fg_hit, grid_for(n, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, d->S, Bc, Rc, PMC, in_w, it, isub, qin,
+             P.fgl.p, P.fglen.p, out_w, P.lkq.p, lk_w);
       if (it < fg_bounces) trace_shadow_slots(c, Bc, RayCount{out_w, 0, 0});
       const bool lds = lookup_lds(d);
       launch(lds ? k_pm_lookup<true> : k_pm_lookup<false>, (unsigned)((long long)d->cus * d->per_cu_lookup[lds]), 64,
@@ -471,7 +472,7 @@ void enqueue_photon_mapping(BatchCtx& c, const Batch& Bc, const RenderConst& Rc,
       qin ^= 1;
     }
   }
-  launch((d->glossy == kGLCoated ? k_pm_finish<kGLCoated> : d->glossy ? k_pm_finish<kGLGlossy> : k_pm_finish<kGLNone>), grid_for(n, 64), 64, 0, P.stream, d->S, Bc, Rc, PMC, n);
+  launch(K.pm_finish, grid_for(n, 64), 64, 0, P.stream, d->S, Bc, Rc, PMC, n);
 }
 
 // What follows the direct light at the camera hits: photon mapping's
@@ -481,7 +482,7 @@ void enqueue_post_direct(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, lo
   hipStream_t s = c.P->stream;
   if (fp.pm) enqueue_photon_mapping(c, Bc, Rc, n);
   if (fp.cmap && fp.PMC.cmap.n != 0)  // causticMap.ready()
-    launch((c.d->glossy == kGLCoated ? k_pt_caustic<kGLCoated> : c.d->glossy ? k_pt_caustic<kGLGlossy> : k_pt_caustic<kGLNone>), grid_for(n, 64), 64, 0, s, c.d->S, Bc, fp.PMC, n);
+    launch(shade_kernels(c.d).pt_caustic, grid_for(n, 64), 64, 0, s, c.d->S, Bc, fp.PMC, n);
   if (fp.ao) launch(k_resolve_ao, grid_for(n), 256, 0, s, c.d->S, Bc, Rc, fp.AOC, n);
 }
 
@@ -490,6 +491,7 @@ void enqueue_post_direct(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, lo
 // primary trace and shading, direct light, the sub-paths' bounces, the ending.
 void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long long n, long long node_base) {
   yk_device* d = c.d;
+  const ShadeKernels& K = shade_kernels(d);
   const FramePlan& fp = *c.fp;
   hipStream_t s = c.P->stream;
   const bool merged = fp.merged;  // never with specular recursion
@@ -509,8 +511,7 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   // z_channel: the camera samples' depth, before the specular recursion's
   // later generations reuse the hit records
   if (c.zs && node_base == 0) launch(k_depth_samples, grid_for(n), 256, 0, s, Bc.p_rays, Bc.p_hits, c.zs, c.DC, n);
-  launch(shade_primary_fn(d->diff_only, d->xl_lights, fp.ao, d->glossy), grid_for(n, YK_PRIMARY_BLOCK), YK_PRIMARY_BLOCK, 0, s,
-         d->S, Bc, Rc, n, qw(c, 0, 0), fp.AOC);
+  launch(K.primary[fp.ao], grid_for(n, YK_PRIMARY_BLOCK), YK_PRIMARY_BLOCK, 0, s, d->S, Bc, Rc, n, qw(c, 0, 0), fp.AOC);
   if (!merged) {
     trace_shadow_slots(c, Bc, RayCount{qw(c, 0, 0), 0, 0});
     launch(k_resolve_primary, grid_for(n), 256, 0, s, Bc, Rc, n);
@@ -518,11 +519,9 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   if (!post_direct_after_bounces) enqueue_post_direct(c, Bc, Rc, n);
   // sub-path index outermost: pathCol is shared across sub-paths and
   // accumulated in the reference's order (pathtracer.cc:164-298)
-  const int bblock = bounce_block(d->diff_only);
   for (int isub = 0; isub < (fp.path ? fp.nsub : 0); ++isub) {
     if (isub > 0)  // sub-path 0's first segment came out of k_shade_primary
-      launch(d->glossy == kGLCoated ? k_path_start<false, kGLCoated> : d->glossy ? k_path_start<false, kGLGlossy> : (d->diff_only ? k_path_start<true> : k_path_start<false>), grid_for(n, YK_BOUNCE_BLOCK), YK_BOUNCE_BLOCK, 0,
-             s, d->S, Bc, Rc, n, isub, qw(c, isub, 0));
+      launch(K.path_start, grid_for(n, YK_BOUNCE_BLOCK), YK_BOUNCE_BLOCK, 0, s, d->S, Bc, Rc, n, isub, qw(c, isub, 0));
     int qin = 1;
     for (int depth = 1; depth <= fp.bounces; ++depth) {
       const unsigned long long* in_w = qw(c, isub, depth - 1);
@@ -533,8 +532,7 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
         Bd = merged_region(Bc, depth);
         Bd.mq_words = qw(c, 0, 0);
       }
-      launch(shade_bounce_fn(d->diff_only, d->xl_lights, d->glossy), grid_for(n, bblock), bblock, 0, s, d->S, Bd, Rc, in_w, depth,
-             isub, qin, out_w);
+      launch(K.bounce, grid_for(n, K.bounce_block), K.bounce_block, 0, s, d->S, Bd, Rc, in_w, depth, isub, qin, out_w);
       if (!merged) {
         trace_shadow_slots(c, Bc, RayCount{out_w, 0, 0});
         launch(k_resolve_bounce, grid_for(n), 256, 0, s, Bc, Rc, in_w, depth, qin);
@@ -545,7 +543,7 @@ void enqueue_entries(BatchCtx& c, const Batch& Bc, const RenderConst& Rc, long l
   if (post_direct_after_bounces) enqueue_post_direct(c, Bc, Rc, n);
   if (d->spec) {
     launch(k_finish_spec, grid_for(n), 256, 0, s, Bc, Rc, c.NS, node_base, n);
-    launch(d->glossy == kGLCoated ? k_spawn<kGLCoated> : k_spawn<kGLNone>, grid_for(n), 256, 0, s, d->S, Bc, Rc, c.NS, node_base, n);
+    launch(K.spawn, grid_for(n), 256, 0, s, d->S, Bc, Rc, c.NS, node_base, n);
   } else if (merged) {  // one any-hit launch for the camera hits and all bounces, then one resolve
     trace_shadow_slots(c, Bc, RayCount{qw(c, 0, 0), 0, 0, fp.plan.regions});
     launch(k_resolve_merged, grid_for(n), 256, 0, s, Bc, Rc, n, fp.bounces);

@@ -344,7 +344,7 @@ extern "C" int yk_debug_shading_kind(yk_device* d, int32_t* diff_only) {
     return set_error(YK_ERR_UNSUPPORTED, "yk_debug_shading_kind: test hook disabled (YK_DEBUG_HOOKS=1)");
   if (!d || !diff_only) return set_error(YK_ERR_ARG, "yk_debug_shading_kind: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_shading_kind: no scene uploaded");
-  *diff_only = d->diff_only ? 1 : 0;
+  *diff_only = d->shade.mat == kMatDiffuse ? 1 : 0;
   return YK_OK;
 }
 

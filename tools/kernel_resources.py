@@ -6,13 +6,14 @@ flags. No GPU is needed.
   tools/kernel_resources.py table [SRC]       print one line per kernel
   tools/kernel_resources.py diff OLD NEW      compare two saved tables
 
-Kernel names are demangled, and the trailing template argument GL (the scene
-holds a glossy material; since the coated glossy material a level: 0 none,
-1 glossy, 2 coated glossy, where 1 is listed as `true`, the flag's earlier
-spelling) is dropped where it is `false` or 0, its default: the
-table lists k_shade_primary<false, 0, false, false> as
-k_shade_primary<false, 0, false> and k_photon_hit<false> as k_photon_hit, so
-tables from before and after a kernel gained the argument line up.
+Kernel names are demangled, and the trailing template argument GL (the scene's
+glossy level: kGLNone 0, kGLGlossy 1, kGLCoated 2) is listed the way the
+tables in profiles/ have listed it since it was a flag: dropped where it is 0
+(or `false`), its default, and `true` where it is 1. The table lists
+k_shade_primary<false, 0, false, 0> as k_shade_primary<false, 0, false>,
+k_shade_primary<false, 0, false, 1> as k_shade_primary<false, 0, false, true>
+and k_photon_hit<0> as k_photon_hit, so tables from before and after a kernel
+gained the argument, or the argument became a level, line up.
 """
 import os
 import re
