@@ -18,6 +18,7 @@ YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT, YK_MAT_GLOSSY = 0, 1, 2
 YK_MAT_COATED_GLOSSY = 4  # 3 is unassigned and refused
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_LIGHT_MESH = 5
+YK_LIGHT_SUN = 6
 YK_MESH_LIGHT_MAX_TRIS, YK_MESH_LIGHT_MAX_DEPTH = 65536, 29
 YK_MESH_SMOOTH, YK_MESH_NORMALS_EXPORTED = 1, 2
 YK_INTEGRATOR_DIRECT, YK_INTEGRATOR_PATH, YK_INTEGRATOR_PHOTON = 0, 1, 2
@@ -101,6 +102,11 @@ class yk_spot_light_state(C.Structure):
 class yk_sphere_light_state(C.Structure):
     _fields_ = [("center", f3), ("radius", C.c_float), ("square_radius", C.c_float),
                 ("square_radius_epsilon", C.c_float), ("area", C.c_float), ("color", f3), ("samples", C.c_int32)]
+
+
+class yk_sun_light_state(C.Structure):
+    _fields_ = [("color", f3), ("col_pdf", f3), ("direction", f3), ("du", f3), ("dv", f3),
+                ("pdf", C.c_float), ("invpdf", C.c_float), ("cos_angle", C.c_double), ("samples", C.c_int32)]
 
 
 class yk_mesh_light(C.Structure):
@@ -256,6 +262,8 @@ SIGNATURES = {
     "yk_scene_get_dirac_light_state": (C.c_int, [P, i32, C.POINTER(yk_dirac_light_state)]),
     "yk_scene_add_spot_light_state": (C.c_int, [P, C.POINTER(yk_spot_light_state)]),
     "yk_scene_get_spot_light_state": (C.c_int, [P, i32, C.POINTER(yk_spot_light_state)]),
+    "yk_scene_add_sun_light_state": (C.c_int, [P, C.POINTER(yk_sun_light_state)]),
+    "yk_scene_get_sun_light_state": (C.c_int, [P, i32, C.POINTER(yk_sun_light_state)]),
     "yk_scene_add_sphere_light_state": (C.c_int, [P, C.POINTER(yk_sphere_light_state)]),
     "yk_scene_get_sphere_light_state": (C.c_int, [P, i32, C.POINTER(yk_sphere_light_state)]),
     "yk_scene_add_mesh_light": (C.c_int, [P, C.POINTER(yk_mesh_light), i32p, i32]),

@@ -249,12 +249,43 @@ yk_sphere_light_state sphere_state(const yk_light& l) {
   return o;
 }
 
+// sunLight_t::sunLight_t, sunlight.cc:52-63, with the source's types:
+// direction.normalize() normalizes the member while createCS takes the
+// constructor's argument `dir` as given (un-normalized: du is its xy part
+// normalized, dv = dir ^ du is as long as dir); angle is clamped to 80;
+// cosAngle is a double holding the float fCos of degToRad(angle) (a double
+// product) rounded to fCos's float parameter; invpdf = M_2PI * (1.f - cosAngle)
+// and pdf = 1.0 / invpdf are double expressions stored to float.
+yk_sun_light_state sun_state(const yk_light& l) {
+  yk_sun_light_state o{};
+  float d[3] = {l.direction[0], l.direction[1], l.direction[2]};
+  create_cs(d, o.du, o.dv);
+  float len = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];  // vector3d_t::normalize, vector3d.h:249-260
+  if (len != 0.f) {
+    len = 1.0f / std::sqrt(len);
+    for (float& x : d) x *= len;
+  }
+  float angle = l.cone_angle;
+  if (angle > 80.f) angle = 80.f;
+  o.cos_angle = (double)host_fcos((float)((double)angle * 0.01745329251994329576922));
+  o.invpdf = (float)(6.28318530717958647692 * ((double)1.f - o.cos_angle));
+  o.pdf = (float)(1.0 / (double)o.invpdf);
+  for (int k = 0; k < 3; ++k) {
+    o.direction[k] = d[k];
+    o.color[k] = l.color[k] * l.power;
+    o.col_pdf[k] = o.color[k] * o.pdf;
+  }
+  o.samples = l.samples;
+  return o;
+}
+
 int light_slots(const Scene& s, size_t i) {
   switch (s.light_kind[i]) {
     case YK_LIGHT_AREA: return 2 * s.light_states[i].samples;  // light samples + BSDF (MIS) samples
     case YK_LIGHT_SPOT: return s.spot_states[i].soft_shadows ? 2 * s.spot_states[i].samples : 1;
     case YK_LIGHT_SPHERE: return s.sphere_states[i].samples;  // canIntersect() is false: no MIS half
     case YK_LIGHT_MESH: return 2 * s.mesh_lights[i].params.samples;  // canIntersect(): light + BSDF halves
+    case YK_LIGHT_SUN: return 2 * s.sun_states[i].samples;           // canIntersect(): light + BSDF halves
     default: return 1;
   }
 }
@@ -361,6 +392,7 @@ void Scene::add_light(const yk_light& l) {
   spot_states.push_back(l.type == YK_LIGHT_SPOT ? spot_state(l) : yk_spot_light_state{});
   sphere_states.push_back(l.type == YK_LIGHT_SPHERE ? sphere_state(l) : yk_sphere_light_state{});
   mesh_lights.emplace_back();
+  sun_states.push_back(l.type == YK_LIGHT_SUN ? sun_state(l) : yk_sun_light_state{});
 }
 void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   lights.push_back(yk_light{});
@@ -373,6 +405,7 @@ void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
+  sun_states.push_back(yk_sun_light_state{});
 }
 void Scene::add_light_state(const yk_area_light_state& l) {
   lights.push_back(yk_light{});
@@ -383,6 +416,7 @@ void Scene::add_light_state(const yk_area_light_state& l) {
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
+  sun_states.push_back(yk_sun_light_state{});
 }
 void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   lights.push_back(yk_light{});
@@ -395,6 +429,7 @@ void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   spot_states.push_back(l);
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
+  sun_states.push_back(yk_sun_light_state{});
 }
 void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   lights.push_back(yk_light{});
@@ -407,6 +442,20 @@ void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(l);
   mesh_lights.emplace_back();
+  sun_states.push_back(yk_sun_light_state{});
+}
+void Scene::add_sun_light_state(const yk_sun_light_state& l) {
+  lights.push_back(yk_light{});
+  light_has_params.push_back(false);
+  light_kind.push_back(YK_LIGHT_SUN);
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(a);
+  dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.emplace_back();
+  sun_states.push_back(l);
 }
 // meshLight_t::factory (meshlight.cc:221-236): color * (CFLOAT)power * M_PI,
 // both through color_t's operator*(color_t, CFLOAT): float products
@@ -431,6 +480,7 @@ void Scene::add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int n
   spot_states.push_back(yk_spot_light_state{});
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.push_back(std::move(m));
+  sun_states.push_back(yk_sun_light_state{});
   built = false;
 }
 void Scene::set_camera(const yk_camera& c) {

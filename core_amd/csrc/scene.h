@@ -66,6 +66,7 @@ struct Scene {
   std::vector<yk_spot_light_state> spot_states;     // spot lights (zero entry for every other kind)
   std::vector<yk_sphere_light_state> sphere_states; // sphere lights (zero entry for every other kind)
   std::vector<MeshLight> mesh_lights;               // mesh lights (empty entry for every other kind)
+  std::vector<yk_sun_light_state> sun_states;       // sun lights (zero entry for every other kind)
   bool has_background = false;
   float background[3] = {0.f, 0.f, 0.f};            // constBackground_t::color (color*power)
   yk_camera_state camera_state{};
@@ -78,6 +79,7 @@ struct Scene {
   void add_dirac_light_state(const yk_dirac_light_state& l);
   void add_spot_light_state(const yk_spot_light_state& l);
   void add_sphere_light_state(const yk_sphere_light_state& l);
+  void add_sun_light_state(const yk_sun_light_state& l);
   void add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int nobj);
   void set_camera(const yk_camera& c);
   void set_camera_state(const yk_camera_state& c);
@@ -112,6 +114,8 @@ yk_dirac_light_state dirac_state(const yk_light& l);
 // spotLight_t ctor (spotlight.cc:63-75), sphereLight_t ctor (spherelight.cc:64-72)
 yk_spot_light_state spot_state(const yk_light& l);
 yk_sphere_light_state sphere_state(const yk_light& l);
+// sunLight_t ctor (sunlight.cc:52-63)
+yk_sun_light_state sun_state(const yk_light& l);
 // shadow slots of one doLightEstimation of scene light i (DLight.nslots)
 int light_slots(const Scene& s, size_t i);
 yk_camera_state camera_state(const yk_camera& c);

@@ -116,6 +116,17 @@ struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-4
   // the light's record in DScene::ml (cdf, triangles, normals, its own tree)
   int double_sided;
   int mesh;
+  // sunLight_t members (sunlight.cc:42-49): dir = direction, du / dv, samples,
+  // and, after init(scene), epos = worldCenter, wradius = worldRadius. `color`
+  // holds colPdf -- what illumSample and intersect hand doLightEstimation as
+  // ls.col / lcol, which is what the sampling loops and resolve_light read
+  // there -- and sun_color the member `color` (totalEnergy). soft = 1 puts the
+  // light among the sampled ones (light_sampled). cosAngle is a double, held
+  // as its two words so that the record keeps its 4-byte alignment.
+  float sun_color[3];
+  float pdf, invpdf;
+  unsigned cos_angle_w[2];
+  float epdf;
 };
 
 // One mesh light's arrays, resident per device handle (yk_device_upload) and
@@ -2778,6 +2789,31 @@ __device__ __forceinline__ bool sphere_hit(const DLight& L, v3 from, v3 dir, flo
   return true;
 }
 
+__device__ __forceinline__ double sun_cos_angle(const DLight& L) {
+  return __hiloint2double((int)L.cos_angle_w[1], (int)L.cos_angle_w[0]);
+}
+
+// sunLight_t::illumSample, sunlight.cc:74-85: a direction inside the cone
+// around `direction`, whatever the point; sampleCone's maxCosAng parameter is
+// a float, which the double cosAngle is converted to at the call. tmax = -1:
+// unbounded. ls.col = colPdf (L.color), ls.pdf = pdf. Always true.
+__device__ __forceinline__ bool sun_illum(const DLight& L, float s1, float s2, v3& ldir, float& tmax, float& pdf) {
+  ldir = sample_cone(ld3(L.dir), ld3(L.du), ld3(L.dv), (float)sun_cos_angle(L), s1, s2);
+  tmax = -1.f;
+  pdf = L.pdf;
+  return true;
+}
+
+// sunLight_t::intersect, sunlight.cc:87-95: the float cosine against the
+// double cosAngle; t = -1 (the shadow ray stays unbounded), col = colPdf
+__device__ __forceinline__ bool sun_hit(const DLight& L, v3 dir, float& t, float& ipdf) {
+  const float cosine = vdot(dir, ld3(L.dir));
+  if ((double)cosine < sun_cos_angle(L)) return false;
+  t = -1.f;
+  ipdf = L.invpdf;
+  return true;
+}
+
 // pdf1D_t::DSample (sample_utils.h:141-157): u == 0 answers 0; otherwise
 // std::lower_bound over cdf[0..n] (the first entry >= u), minus 1, clamped at 0
 __device__ __forceinline__ int mesh_dsample(const float* cdf, int n, float u) {
@@ -3525,9 +3561,10 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
 // at its isShadowed calls: every shadow ray it would trace is written to its
 // slot with the contribution it adds when unoccluded. Returns #rays; sets bit
 // k of `traced` (k < 64) for each slot that holds a ray.
-// XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light) or
-// kXLMesh (it holds a mesh light; ml = DScene::ml): see kShade
-constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2;
+// XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light),
+// kXLMesh (it holds a mesh light; ml = DScene::ml) or kXLSun (it holds a sun
+// light); each level holds the code of those below it: see kShade
+constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2, kXLSun = 3;
 template <bool DIFF = false, int XL = kXLNone, int GL = kGLNone>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
@@ -3540,7 +3577,9 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
   // outside the sample loops
   if (L.type == YK_LIGHT_AREA)
     return gen_sampled<DIFF, YK_LIGHT_AREA, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
-  if (XL == kXLMesh && L.type == YK_LIGHT_MESH)
+  if (XL >= kXLSun && L.type == YK_LIGHT_SUN)
+    return gen_sampled<DIFF, YK_LIGHT_SUN, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  if (XL >= kXLMesh && L.type == YK_LIGHT_MESH)
     return gen_sampled<DIFF, YK_LIGHT_MESH, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced, ml + L.mesh);
   if (XL && L.type == YK_LIGHT_SPHERE)
     return gen_sampled<DIFF, YK_LIGHT_SPHERE, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
@@ -3576,7 +3615,11 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 // its sample function, its intersect function and ls.col / lcol -- the
 // colour as is for area, sphere and mesh lights, the colour times the cone's
 // falloff cv for a soft spot (kept in the slot's aux record under
-// transparent shadows, which filter the colour first). A sphere light's
+// transparent shadows, which filter the colour first), colPdf for a sun
+// (DLight::color holds it). A sun's rays are unbounded (t = -1) in both
+// halves; the split slot form marks a BSDF-half ray by the sign of its w, so
+// there the unbounded one is stored as -inf (unpack_shadow: tmax = +inf, which
+// the any-hit traversal takes as it takes a negative tmax). A sphere light's
 // canIntersect() is false (spherelight.cc:49): no MIS weight on its light
 // samples and no BSDF half, so it owns `samples` slots, not 2 * samples.
 template <bool DIFF, int KIND, int GL>
@@ -3603,6 +3646,7 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
     if (KIND == YK_LIGHT_AREA) lit = light_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
     else if (KIND == YK_LIGHT_MESH) lit = mesh_illum(L, *ml, sp.P, s1, s2, ldir, ltmax, lpdf, tri);
     else if (KIND == YK_LIGHT_SPOT) lit = spot_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf, cv);
+    else if (KIND == YK_LIGHT_SUN) lit = sun_illum(L, s1, s2, ldir, ltmax, lpdf);
     else lit = sphere_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
     if (!lit) {
       put_slot(B, slot, 0, black);
@@ -3651,13 +3695,15 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
       int tri;
       if (KIND == YK_LIGHT_AREA) hit = light_hit(L, sp.P, bdir, bt, lightPdf);
       else if (KIND == YK_LIGHT_MESH) hit = mesh_hit(L, *ml, sp.P, bdir, bt, lightPdf, tri);
+      else if (KIND == YK_LIGHT_SUN) hit = sun_hit(L, bdir, bt, lightPdf);
       else hit = spot_hit(L, sp.P, bdir, bt, lightPdf, cv);
     }
     if (!hit) {
       put_slot(B, slot, 0, black);
       continue;
     }
-    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0; mesh: bt >= MIN_RAYDIST
+    if (KIND == YK_LIGHT_SUN && B.split) bt = __uint_as_float(0x7f800000u);  // unbounded, as a MIS record holds it
+    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0; mesh: bt >= MIN_RAYDIST; sun: -1
     if (!(lightPdf > 1e-6f)) {
       put_slot(B, slot, SL_TRACED, black);
       continue;
@@ -5250,10 +5296,10 @@ constexpr TraceInfo kTrace[kTraceVariants] = {
 // kMatDiffuse: every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>);
 // kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated)
 enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kShadeMats };
-constexpr int kXLLevels = kXLMesh + 1;
+constexpr int kXLLevels = kXLSun + 1;
 struct ShadeVariant {
   int mat = kMatGeneral;  // ShadeMat
-  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light
+  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light; kXLSun: a sun
 };
 struct ShadeKernels {
   decltype(&k_shade_primary<false, kXLNone, false>) primary[2];  // [AO]
@@ -5263,6 +5309,7 @@ struct ShadeKernels {
   decltype(&k_spawn<>) spawn;
   decltype(&k_fg_start<false>) fg_start;
   decltype(&k_fg_hit<false>) fg_hit;
+  decltype(&k_photon_emit<>) photon_emit;
   decltype(&k_pm_post<>) pm_post;
   decltype(&k_pm_finish<>) pm_finish;
   decltype(&k_pt_caustic<>) pt_caustic;
@@ -5284,27 +5331,44 @@ struct ShadeKernels {
 // Only k_shade_primary and k_shade_bounce sample lights, so only they take XL;
 // the photon, k_pm_* and k_pt_caustic kernels take GL alone; k_spawn differs
 // only for the coat (mat_specular), so glossy scenes run the general one.
+// A sun light (kXLSun) is the top level: its cone sampling and cone test, on
+// top of everything below. It is also the one sampled light beyond the area
+// light that photon maps accept, so at this level alone k_fg_hit (whose
+// estimateOneDirectLight may pick the sun) and k_photon_emit (emitPhoton)
+// have instantiations of their own; at every other level they are the
+// kernels they were before the sun.
 template <int MAT, int XL>
 constexpr ShadeKernels shade_cell() {
   constexpr bool DIFF = MAT == kMatDiffuse;
   constexpr int GL = MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
   return {{k_shade_primary<DIFF, XL, false, GL>, k_shade_primary<DIFF, XL, true, GL>}, k_shade_bounce<DIFF, XL, GL>,
           bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL == kGLCoated ? kGLCoated : kGLNone)>,
-          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>, k_photon_hit<GL>};
+          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL, (XL == kXLSun ? kXLSun : kXLNone)>,
+          k_photon_emit<(XL == kXLSun ? kXLSun : kXLNone)>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>,
+          k_photon_hit<GL>};
 }
 constexpr ShadeKernels kShade[kShadeMats][kXLLevels] = {
-    {shade_cell<kMatDiffuse, kXLNone>(), shade_cell<kMatDiffuse, kXLSpotSphere>(), shade_cell<kMatDiffuse, kXLMesh>()},
-    {shade_cell<kMatGeneral, kXLNone>(), shade_cell<kMatGeneral, kXLSpotSphere>(), shade_cell<kMatGeneral, kXLMesh>()},
-    {shade_cell<kMatGlossy, kXLNone>(), shade_cell<kMatGlossy, kXLSpotSphere>(), shade_cell<kMatGlossy, kXLMesh>()},
-    {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>()},
+    {shade_cell<kMatDiffuse, kXLNone>(), shade_cell<kMatDiffuse, kXLSpotSphere>(), shade_cell<kMatDiffuse, kXLMesh>(),
+     shade_cell<kMatDiffuse, kXLSun>()},
+    {shade_cell<kMatGeneral, kXLNone>(), shade_cell<kMatGeneral, kXLSpotSphere>(), shade_cell<kMatGeneral, kXLMesh>(),
+     shade_cell<kMatGeneral, kXLSun>()},
+    {shade_cell<kMatGlossy, kXLNone>(), shade_cell<kMatGlossy, kXLSpotSphere>(), shade_cell<kMatGlossy, kXLMesh>(),
+     shade_cell<kMatGlossy, kXLSun>()},
+    {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>(),
+     shade_cell<kMatCoated, kXLSun>()},
 };
-// the table names no instantiation beyond today's: no glossy k_spawn, no DIFF or XL where a kernel takes none
+// below the sun's level the table names no instantiation beyond those it named before: no glossy k_spawn, no
+// DIFF or XL where a kernel takes none; the sun's level adds k_fg_hit and k_photon_emit of its own
 static_assert(kShade[kMatGlossy][kXLNone].spawn == kShade[kMatGeneral][kXLNone].spawn &&
               kShade[kMatCoated][kXLNone].spawn != kShade[kMatGeneral][kXLNone].spawn &&
               kShade[kMatDiffuse][kXLNone].photon_hit == kShade[kMatGeneral][kXLNone].photon_hit &&
               kShade[kMatDiffuse][kXLNone].pm_post == kShade[kMatGeneral][kXLNone].pm_post &&
               kShade[kMatCoated][kXLMesh].fg_hit == kShade[kMatCoated][kXLNone].fg_hit &&
-              kShade[kMatDiffuse][kXLMesh].path_start == kShade[kMatDiffuse][kXLNone].path_start);
+              kShade[kMatDiffuse][kXLMesh].path_start == kShade[kMatDiffuse][kXLNone].path_start &&
+              kShade[kMatGeneral][kXLMesh].photon_emit == kShade[kMatDiffuse][kXLNone].photon_emit &&
+              kShade[kMatCoated][kXLSun].fg_hit != kShade[kMatCoated][kXLNone].fg_hit &&
+              kShade[kMatDiffuse][kXLSun].photon_emit != kShade[kMatDiffuse][kXLNone].photon_emit &&
+              kShade[kMatDiffuse][kXLSun].path_start == kShade[kMatDiffuse][kXLNone].path_start);
 
 struct yk_device {
   int ordinal = 0;
@@ -5624,6 +5688,37 @@ DLight make_sphere_light(const yk_sphere_light_state& L) {
   D.sq_radius = L.square_radius;
   D.sq_radius_eps = L.square_radius_epsilon;
   D.area = L.area;
+  return D;
+}
+
+// sunLight_t members as yk_sun_light_state holds them (sunlight.cc:42-49), and
+// init(scene) (sunlight.cc:65-72) on the scene bound {a, g}: worldRadius =
+// 0.5 * (g - a).length() is a double product of the float length, stored to
+// float; worldCenter = 0.5 * (a + g) goes through operator*(PFLOAT, point3d_t),
+// float products; ePdf = M_PI * worldRadius * worldRadius in double, to float
+DLight make_sun_light(const yk_sun_light_state& L, const float* bound) {
+  DLight D{};
+  D.type = YK_LIGHT_SUN;
+  D.soft = 1;  // light_sampled(): doLightEstimation's sample loops
+  D.samples = L.samples;
+  D.nslots = 2 * L.samples;  // cone samples + BSDF (MIS) samples
+  for (int k = 0; k < 3; ++k) {
+    D.dir[k] = L.direction[k];
+    D.du[k] = L.du[k];
+    D.dv[k] = L.dv[k];
+    D.color[k] = L.col_pdf[k];
+    D.sun_color[k] = L.color[k];
+    D.epos[k] = 0.5f * (bound[k] + bound[3 + k]);
+  }
+  D.pdf = L.pdf;
+  D.invpdf = L.invpdf;
+  uint64_t w;
+  std::memcpy(&w, &L.cos_angle, sizeof w);
+  D.cos_angle_w[0] = (unsigned)(w & 0xffffffffu);
+  D.cos_angle_w[1] = (unsigned)(w >> 32);
+  const float dx = bound[3] - bound[0], dy = bound[4] - bound[1], dz = bound[5] - bound[2];
+  D.wradius = (float)(0.5 * (double)std::sqrt(dx * dx + dy * dy + dz * dz));
+  D.epdf = (float)(3.14159265358979323846 * (double)D.wradius * (double)D.wradius);
   return D;
 }
 
@@ -6289,6 +6384,8 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
       lights.push_back(make_spot_light(S.spot_states[i]));
     } else if (S.light_kind[i] == YK_LIGHT_SPHERE) {
       lights.push_back(make_sphere_light(S.sphere_states[i]));
+    } else if (S.light_kind[i] == YK_LIGHT_SUN) {
+      lights.push_back(make_sun_light(S.sun_states[i], S.tree.bound));
     } else {
       lights.push_back(make_dirac_light(S.dirac_states[i]));
       if (lights.back().type == YK_LIGHT_DIRECTIONAL) directional_photon_frame(lights.back(), S.tree.bound);
@@ -6322,6 +6419,8 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
     HIPCHK(hipMemcpy(d->ml_recs.p, ml_recs.data(), ml_recs.size() * sizeof(DMeshLight), hipMemcpyHostToDevice));
     d->S.ml = d->ml_recs.p;
   }
+  for (const DLight& L : lights)
+    if (L.type == YK_LIGHT_SUN) d->shade.xl = kXLSun;
   d->sum_light_slots = sum_slots;
   d->lights_host = lights;
   d->pm_ready = false;

@@ -240,8 +240,21 @@ int yk_scene_add_curve(yk_scene* s, const float* points, int32_t npoints, int32_
 int yk_scene_add_light(yk_scene* s, const yk_light* l) {
   if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_light: NULL argument");
   if (l->type != YK_LIGHT_AREA && l->type != YK_LIGHT_POINT && l->type != YK_LIGHT_DIRECTIONAL &&
-      l->type != YK_LIGHT_SPOT && l->type != YK_LIGHT_SPHERE)
+      l->type != YK_LIGHT_SPOT && l->type != YK_LIGHT_SPHERE && l->type != YK_LIGHT_SUN)
     return set_error(YK_ERR_UNSUPPORTED, "light type not supported");
+  if (l->type == YK_LIGHT_SUN) {
+    const float* d = l->direction;
+    if (!std::isfinite(d[0]) || !std::isfinite(d[1]) || !std::isfinite(d[2]) ||
+        (d[0] == 0.f && d[1] == 0.f && d[2] == 0.f))
+      return set_error(YK_ERR_ARG, "sun light needs a finite, non-zero direction");
+    if (!std::isfinite(l->color[0]) || !std::isfinite(l->color[1]) || !std::isfinite(l->color[2]) ||
+        !std::isfinite(l->power))
+      return set_error(YK_ERR_ARG, "sun light needs a finite colour and power");
+    // angle 0: cosAngle == 1, invpdf == 0 and an infinite pdf (sunlight.cc:59-61)
+    if (!std::isfinite(l->cone_angle) || !(l->cone_angle > 0.f))
+      return set_error(YK_ERR_ARG, "sun light needs a finite angle > 0 (cone_angle carries it)");
+    if (l->samples < 1) return set_error(YK_ERR_ARG, "sun light needs samples >= 1");
+  }
   if (l->type == YK_LIGHT_AREA && l->samples < 1) return set_error(YK_ERR_ARG, "area light needs samples >= 1");
   if (l->type == YK_LIGHT_SPOT) {
     if (l->soft_shadows && l->samples < 1) return set_error(YK_ERR_ARG, "soft-shadow spot light needs samples >= 1");
@@ -403,6 +416,23 @@ int yk_scene_get_sphere_light_state(const yk_scene* s, int32_t i, yk_sphere_ligh
     return set_error(YK_ERR_ARG, "yk_scene_get_sphere_light_state: bad arguments");
   if (s->s.light_kind[i] != YK_LIGHT_SPHERE) return set_error(YK_ERR_STATE, "light is not a sphere light");
   *out = s->s.sphere_states[i];
+  return YK_OK;
+}
+
+int yk_scene_add_sun_light_state(yk_scene* s, const yk_sun_light_state* l) {
+  if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_sun_light_state: NULL argument");
+  if (l->samples < 1) return set_error(YK_ERR_ARG, "sun light needs samples >= 1");
+  YK_GUARD_BEGIN
+  s->s.add_sun_light_state(*l);
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_sun_light_state(const yk_scene* s, int32_t i, yk_sun_light_state* out) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.sun_states.size())
+    return set_error(YK_ERR_ARG, "yk_scene_get_sun_light_state: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_SUN) return set_error(YK_ERR_STATE, "light is not a sun light");
+  *out = s->s.sun_states[i];
   return YK_OK;
 }
 

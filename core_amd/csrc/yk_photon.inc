@@ -312,8 +312,76 @@ __device__ __forceinline__ void store4(float4* p, v3 v) { *p = make_float4(v.x, 
 __device__ __forceinline__ void store4(float4* p, c3 v) { *p = make_float4(v.r, v.g, v.b, 0.f); }
 
 
+// minRot, sample_utils.h:168-176, as written: U2 = cosAlpha*U + (1.f-cosAlpha) * (v*U) + sinAlpha * (v^U),
+// where v*U is the dot product, so the middle term is a float: it becomes
+// vector3d_t(PFLOAT) (vector3d.h:57) and is added to all three components.
+// sinAlpha = fSqrt(1 - cosAlpha*cosAlpha) is NaN where rounding puts
+// cosAlpha a little above 1; it is kept (a NaN frame gives a NaN origin).
+__device__ __forceinline__ void min_rot(v3 D, v3 U, v3 D2, v3& U2, v3& V2) {
+  const float cosAlpha = vdot(D, D2);
+  const float sinAlpha = sqrtf(1.f - cosAlpha * cosAlpha);
+  const v3 v = vcross(D, D2);
+  const float m = (1.f - cosAlpha) * vdot(v, U);
+  const v3 w = vcross(v, U);
+  U2 = V3((cosAlpha * U.x + m) + sinAlpha * w.x, (cosAlpha * U.y + m) + sinAlpha * w.y,
+          (cosAlpha * U.z + m) + sinAlpha * w.z);
+  V2 = vcross(D2, U2);
+}
+
+// light_t::emitPhoton of the lights that photon maps take: the ray, ipdf and
+// the returned colour. XL == kXLSun adds sunLight_t::emitPhoton (sunlight.cc:
+// 97-112) as written: the disk point and the cone direction both come from
+// s3, s4 (s1, s2 are unused), the disk is carried by minRot's frame around
+// ldir, and the colour is colPdf * ePdf.
+template <int XL>
+__device__ __forceinline__ c3 emit_photon(const DLight& L, float s1, float s2, float s3, float s4, v3& from, v3& dir,
+                                          float& ipdf) {
+  if (XL >= kXLSun && L.type == YK_LIGHT_SUN) {
+    float u, v;
+    shirley_disk(s3, s4, u, v);
+    const v3 ldir = sample_cone(ld3(L.dir), ld3(L.du), ld3(L.dv), (float)sun_cos_angle(L), s3, s4);
+    v3 du2, dv2;
+    min_rot(ld3(L.dir), ld3(L.du), ldir, du2, dv2);
+    ipdf = L.invpdf;
+    const v3 off = vadd(vadd(vmul(u, du2), vmul(v, dv2)), ldir);
+    from = vadd(ld3(L.epos), vmul(L.wradius, off));
+    dir = vneg(ldir);
+    return C3(L.color[0] * L.epdf, L.color[1] * L.epdf, L.color[2] * L.epdf);
+  }
+  if (L.type == YK_LIGHT_DIRECTIONAL) {  // directionalLight_t::emitPhoton, directional.cc:106-116
+    dir = vneg(ld3(L.dir));
+    float u, v;
+    shirley_disk(s1, s2, u, v);
+    const v3 off = vadd(vmul(u, ld3(L.edu)), vmul(v, ld3(L.edv)));
+    from = vadd(ld3(L.epos), vmul(L.eradius, off));
+    if (L.infinite) from = vadd(from, vmul(L.wradius, ld3(L.dir)));
+    ipdf = (float)(YK_PI_D * (double)L.eradius * (double)L.eradius);
+  } else if (L.type == YK_LIGHT_POINT) {  // pointLight_t::emitPhoton + SampleSphere (sample_utils.h:54-72)
+    from = ld3(L.pos);
+    dir.z = 1.0f - 2.0f * s1;
+    float rr = 1.0f - dir.z * dir.z;
+    if (rr > 0.0f) {
+      rr = sqrtf(rr);
+      const float a = (float)(YK_2PI_D * (double)s2);
+      dir.x = fcos_ref(a) * rr;
+      dir.y = fsin_ref(a) * rr;
+    } else {
+      dir.x = 0.0f;
+      dir.y = 0.0f;
+    }
+    ipdf = (float)(4.0 * YK_PI_D);
+  } else {  // areaLight_t::emitPhoton, arealight.cc:98-104
+    ipdf = L.area;
+    from = vadd(vadd(ld3(L.corner), vmul(s3, ld3(L.toX))), vmul(s4, ld3(L.toY)));
+    dir = sample_cos_hemisphere(ld3(L.normal), ld3(L.du), ld3(L.dv), s1, s2);
+  }
+  return C3(L.color[0], L.color[1], L.color[2]);
+}
+
 // Photon emission for photon `curr` (photonintegr.cc:224-246): QMC numbers,
 // pdf1D_t::DSample light choice, light_t::emitPhoton, colour scaling.
+// XL: kXLNone, or kXLSun for scenes that hold a sun (emit_photon).
+template <int XL = kXLNone>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_emit(PhotonConst PC, PhotonBuf PB, unsigned long long* qword) {
   const unsigned curr = blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = curr < PC.nphotons;
@@ -335,35 +403,9 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_photon_emit(PhotonConst PC,
     const DLight& L = c_lights[ln];
     v3 from, dir;
     float ipdf;
-    if (L.type == YK_LIGHT_DIRECTIONAL) {  // directionalLight_t::emitPhoton, directional.cc:106-116
-      dir = vneg(ld3(L.dir));
-      float u, v;
-      shirley_disk(s1, s2, u, v);
-      const v3 off = vadd(vmul(u, ld3(L.edu)), vmul(v, ld3(L.edv)));
-      from = vadd(ld3(L.epos), vmul(L.eradius, off));
-      if (L.infinite) from = vadd(from, vmul(L.wradius, ld3(L.dir)));
-      ipdf = (float)(YK_PI_D * (double)L.eradius * (double)L.eradius);
-    } else if (L.type == YK_LIGHT_POINT) {  // pointLight_t::emitPhoton + SampleSphere (sample_utils.h:54-72)
-      from = ld3(L.pos);
-      dir.z = 1.0f - 2.0f * s1;
-      float rr = 1.0f - dir.z * dir.z;
-      if (rr > 0.0f) {
-        rr = sqrtf(rr);
-        const float a = (float)(YK_2PI_D * (double)s2);
-        dir.x = fcos_ref(a) * rr;
-        dir.y = fsin_ref(a) * rr;
-      } else {
-        dir.x = 0.0f;
-        dir.y = 0.0f;
-      }
-      ipdf = (float)(4.0 * YK_PI_D);
-    } else {  // areaLight_t::emitPhoton, arealight.cc:98-104
-      ipdf = L.area;
-      from = vadd(vadd(ld3(L.corner), vmul(s3, ld3(L.toX))), vmul(s4, ld3(L.toY)));
-      dir = sample_cos_hemisphere(ld3(L.normal), ld3(L.du), ld3(L.dv), s1, s2);
-    }
+    const c3 ecol = emit_photon<XL>(L, s1, s2, s3, s4, from, dir, ipdf);
     const float k = (PC.fnum_lights * ipdf) / lightNumPdf;
-    const c3 pcol = C3(L.color[0] * k, L.color[1] * k, L.color[2] * k);
+    const c3 pcol = C3(ecol.r * k, ecol.g * k, ecol.b * k);
     if (!cblack(pcol)) {
       emit = true;
       PB.pcol[3 * (size_t)curr] = pcol.r;
@@ -619,7 +661,9 @@ __global__ void __launch_bounds__(YK_APPEND_BLOCK) k_fg_start(DScene S, Batch B,
 #ifndef YK_FG_WAVES_D
 #define YK_FG_WAVES_D 1  // occupancy target of the diffuse-only k_fg_hit (1: the compiler's choice)
 #endif
-template <bool DIFF, int GL = kGLNone>
+// XL: kXLNone, or kXLSun for scenes that hold a sun, the one light beyond the
+// area, point and directional lights that yk_photon_build accepts (gen_light).
+template <bool DIFF, int GL = kGLNone, int XL = kXLNone>
 __global__ void __launch_bounds__(YK_APPEND_BLOCK) __attribute__((amdgpu_waves_per_eu(DIFF ? YK_FG_WAVES_D : 1)))
 k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
                                                 const unsigned long long* __restrict__ qin_word, int it, int isub,
@@ -688,7 +732,7 @@ k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
               hal_start(h2, 2u, (unsigned)((int)offs - 1));
               int lnum = (int)(hal_next(h2) * (float)R.nlights);
               if (lnum > R.nlights - 1) lnum = R.nlights - 1;
-              nr = gen_light<DIFF, kXLNone, GL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced);
+              nr = gen_light<DIFF, XL, GL>(B, c, 0, lnum, sp, pwo, s, B.soffs[c], (unsigned)lnum, traced, c_mats, S.ml);
               kend = c_lights[lnum].nslots;
               if (nr) put_org(B, c, sp.P);
               B.lsel[c] = lnum;

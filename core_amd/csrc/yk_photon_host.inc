@@ -12,12 +12,14 @@ constexpr int kMaxPointTreeDepth = kPStack - 2;
 
 // light_t::totalEnergy().energy(): areaLight_t color * area (arealight.cc:66),
 // pointLight_t color * 4.0f * M_PI (pointlight.cc:32), directionalLight_t
-// color * radius*radius * M_PI (directional.cc:33); energy() = (R+G+B)*0.333333f
+// color * radius*radius * M_PI (directional.cc:33), sunLight_t color * ePdf
+// (sunlight.cc:32); energy() = (R+G+B)*0.333333f
 float light_energy(const DLight& L) {
   float e[3];
   for (int k = 0; k < 3; ++k) {
     if (L.type == YK_LIGHT_POINT) e[k] = (L.color[k] * 4.0f) * (float)YK_PI_D;
     else if (L.type == YK_LIGHT_DIRECTIONAL) e[k] = ((L.color[k] * L.eradius) * L.eradius) * (float)YK_PI_D;
+    else if (L.type == YK_LIGHT_SUN) e[k] = L.sun_color[k] * L.epdf;
     else e[k] = L.color[k] * L.area;
   }
   return ((e[0] + e[1]) + e[2]) * 0.333333f;
@@ -195,7 +197,7 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
     HIPCHK(hipMemsetAsync(words.p, 0, nw * sizeof(unsigned long long), P.stream));
     HIPCHK(hipMemsetAsync(s_flag.p, 0, nslots, P.stream));
     unsigned long long* qwd = words.p + kAccWords;
-    launch(k_photon_emit, grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, C, PB, qwd);
+    launch(shade_kernels(d).photon_emit, grid_for(N, YK_APPEND_BLOCK), YK_APPEND_BLOCK, 0, P.stream, C, PB, qwd);
     int qin = 1;
     for (int b = 0; b <= MB; ++b) {
       unsigned long long* work = words.p + kAccWords + (MB + 2) + 128ll * b;

@@ -46,9 +46,10 @@ __global__ void k_qmc_probe(int fn, const void* in, const uint32_t* in2, long lo
 }
 
 // yk_debug_light_probe: the shading kernels' own light functions (dirac_illum,
-// light_illum / spot_illum / sphere_illum / mesh_illum, light_hit / spot_hit /
-// sphere_hit / mesh_hit) on light li of the bound constants (ml: the handle's
-// mesh-light records); col as gen_light / gen_sampled form it
+// light_illum / spot_illum / sphere_illum / mesh_illum / sun_illum, light_hit /
+// spot_hit / sphere_hit / mesh_hit / sun_hit) on light li of the bound
+// constants (ml: the handle's mesh-light records); col as gen_light /
+// gen_sampled form it. EMIT_PHOTON: k_photon_emit's emit_photon.
 __global__ void k_light_probe(int li, int fn, const float* in, long long n, float* out, const DMeshLight* ml) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -60,6 +61,24 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   float tmax = 0.f, pdf = 0.f, cv = 1.f;
   int tri = 0;
   c3 col = C3(0.f, 0.f, 0.f);
+  if (fn == YK_LIGHT_PROBE_EMIT_PHOTON) {
+    const float* x = in + 4 * i;
+    if (L.type != YK_LIGHT_AREA && L.type != YK_LIGHT_POINT && L.type != YK_LIGHT_DIRECTIONAL && L.type != YK_LIGHT_SUN)
+      return;  // yk_photon_build refuses the others
+    v3 from = V3(0.f, 0.f, 0.f);
+    col = emit_photon<kXLSun>(L, x[0], x[1], x[2], x[3], from, dir, pdf);
+    o[0] = from.x;
+    o[1] = from.y;
+    o[2] = from.z;
+    o[3] = dir.x;
+    o[4] = dir.y;
+    o[5] = dir.z;
+    o[6] = pdf;
+    o[7] = col.r;
+    o[8] = col.g;
+    o[9] = col.b;
+    return;
+  }
   if (fn == YK_LIGHT_PROBE_ILLUMINATE) {
     const bool dirac = L.type == YK_LIGHT_POINT || L.type == YK_LIGHT_DIRECTIONAL || L.type == YK_LIGHT_SPOT;
     if (!(dirac && dirac_illum(L, ld3(in + 3 * i), dir, tmax, col))) return;
@@ -70,6 +89,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
     else if (L.type == YK_LIGHT_SPOT) ok = spot_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf, cv);
     else if (L.type == YK_LIGHT_SPHERE) ok = sphere_illum(L, ld3(x), x[3], x[4], dir, tmax, pdf);
     else if (L.type == YK_LIGHT_MESH) ok = mesh_illum(L, ml[L.mesh], ld3(x), x[3], x[4], dir, tmax, pdf, tri);
+    else if (L.type == YK_LIGHT_SUN) ok = sun_illum(L, x[3], x[4], dir, tmax, pdf);
     if (!ok) return;
     col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
   } else {
@@ -80,6 +100,7 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
     else if (L.type == YK_LIGHT_SPOT) ok = spot_hit(L, ld3(x), ld3(x + 3), t, pdf, cv);
     else if (L.type == YK_LIGHT_SPHERE) ok = sphere_hit(L, ld3(x), ld3(x + 3), pdf);
     else if (L.type == YK_LIGHT_MESH) ok = mesh_hit(L, ml[L.mesh], ld3(x), ld3(x + 3), t, pdf, tri);
+    else if (L.type == YK_LIGHT_SUN) ok = sun_hit(L, ld3(x + 3), t, pdf);
     if (!ok) return;
     col = L.type == YK_LIGHT_SPOT ? cscale(cv, lcol) : lcol;
     o[0] = 1.f;
@@ -268,6 +289,7 @@ extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t f
     case YK_LIGHT_PROBE_ILLUMINATE: in_f = 3; break;
     case YK_LIGHT_PROBE_ILLUM_SAMPLE: in_f = 5; break;
     case YK_LIGHT_PROBE_INTERSECT: in_f = 6; break;
+    case YK_LIGHT_PROBE_EMIT_PHOTON: in_f = 4; break;
     default: return set_error(YK_ERR_ARG, "yk_debug_light_probe: unknown function");
   }
   if (n == 0) return YK_OK;

@@ -136,6 +136,13 @@ class Scene:
                        from_=A.f3(*from_), radius=radius)
         A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
 
+    def add_sun_light(self, direction, color=(1, 1, 1), power=1.0, angle=0.27, samples=4):
+        """sunlight (sunlight.cc:115-130); angle is the half angle of the sun's disc in degrees
+        (clamped to 80), carried by yk_light::cone_angle"""
+        l = A.yk_light(type=A.YK_LIGHT_SUN, color=A.f3(*color), power=power, samples=samples,
+                       direction=A.f3(*direction), cone_angle=angle)
+        A.check(A.lib().yk_scene_add_light(self._p, C.byref(l)))
+
     def add_mesh_light(self, obj_ids, color=(1, 1, 1), power=1.0, samples=4, double_sided=False):
         """meshlight (meshlight.cc:221-236) over the triangles of the TRIM meshes obj_ids (one id or a
         list), concatenated in the order given"""
@@ -224,15 +231,19 @@ class Scene:
     def add_sphere_light_state(self, st):
         A.check(A.lib().yk_scene_add_sphere_light_state(self._p, C.byref(st)))
 
+    def add_sun_light_state(self, st):
+        A.check(A.lib().yk_scene_add_sun_light_state(self._p, C.byref(st)))
+
     def light_states(self):
         """Per light: yk_area_light_state, yk_dirac_light_state, yk_spot_light_state,
-        yk_sphere_light_state or yk_mesh_light_state (each getter answers YK_ERR_STATE for
+        yk_sphere_light_state, yk_sun_light_state or yk_mesh_light_state (each getter answers YK_ERR_STATE for
         the other kinds; a mesh light's state needs a built scene)."""
         L = A.lib()
         getters = ((A.yk_area_light_state, L.yk_scene_get_area_light_state),
                    (A.yk_dirac_light_state, L.yk_scene_get_dirac_light_state),
                    (A.yk_spot_light_state, L.yk_scene_get_spot_light_state),
                    (A.yk_sphere_light_state, L.yk_scene_get_sphere_light_state),
+                   (A.yk_sun_light_state, L.yk_scene_get_sun_light_state),
                    (A.yk_mesh_light_state, lambda p, k, m: L.yk_scene_get_mesh_light_state(p, k, m, None, None, 0)))
         out = []
         for k in range(self.info().nlights):

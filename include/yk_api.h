@@ -97,7 +97,7 @@ enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
  * yk_scene_add_light answers YK_ERR_UNSUPPORTED for it (yk_light has no room
  * for object ids). */
 enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2, YK_LIGHT_SPOT = 3, YK_LIGHT_SPHERE = 4,
-       YK_LIGHT_MESH = 5 };
+       YK_LIGHT_MESH = 5, YK_LIGHT_SUN = 6 };
 typedef struct yk_light {
   int32_t type;
   /* area: areaLight_t::factory, arealight.cc:171-192 */
@@ -120,7 +120,14 @@ typedef struct yk_light {
    * sphere: sphereLight_t::factory (spherelight.cc:196-213): from [0,0,0]
    * (the centre), color [1,1,1], power [1], radius [1], samples [4]; its
    * "object" link is not on the path. Appended fields only: the offsets
-   * above are what earlier callers compiled against. */
+   * above are what earlier callers compiled against.
+   * sun: sunLight_t::factory (sunlight.cc:115-130): direction [0,0,1], color
+   * [1,1,1], power [1], angle [0.27, degrees, the half angle of the sun's
+   * disc], samples [4]; a zero-initialised struct must set them. The struct
+   * does not grow for it: `cone_angle` carries the sun's "angle" (above 80 it
+   * is clamped to 80, as the constructor does). YK_ERR_ARG for a zero or
+   * non-finite direction, a non-finite colour or power, an angle that is not
+   * finite or <= 0 (cosAngle == 1: invpdf 0, pdf infinite) and samples < 1. */
   float to[3];
   float cone_angle;
   float blend;
@@ -532,6 +539,16 @@ typedef struct yk_sphere_light_state { /* sphereLight_t members after its ctor (
   int32_t samples;
 } yk_sphere_light_state;
 
+typedef struct yk_sun_light_state { /* sunLight_t members after its ctor (sunlight.cc:52-63) */
+  float color[3];           /* color * power                                            */
+  float col_pdf[3];         /* colPdf = color * pdf                                     */
+  float direction[3];       /* normalized                                               */
+  float du[3], dv[3];       /* createCS of the constructor's UN-normalized argument     */
+  float pdf, invpdf;        /* invpdf = M_2PI * (1.f - cosAngle), pdf = 1.0 / invpdf: in double, stored to float */
+  double cos_angle;         /* cosAngle: a double holding the float fCos((float)degToRad(angle)) */
+  int32_t samples;
+} yk_sun_light_state;
+
 typedef struct yk_camera_state { /* the camera after its ctor and setAxis (perspectiveCamera.cc:57-71) */
   float position[3], vright[3], vup[3], vto[3], cam_z[3];
   float near_p[3], far_p[3]; /* near_plane.p / far_plane.p (camera.h:54-57)            */
@@ -576,6 +593,16 @@ int yk_scene_add_spot_light_state(yk_scene* s, const yk_spot_light_state* l);
 int yk_scene_get_spot_light_state(const yk_scene* s, int32_t i, yk_spot_light_state* out);
 int yk_scene_add_sphere_light_state(yk_scene* s, const yk_sphere_light_state* l);
 int yk_scene_get_sphere_light_state(const yk_scene* s, int32_t i, yk_sphere_light_state* out);
+/* sun light: `samples` cone samples and as many BSDF (MIS) samples per
+ * estimate (sunLight_t::canIntersect() is true), all unbounded rays. Its
+ * photon members (worldCenter, worldRadius, ePdf: sunLight_t::init) come from
+ * the scene bound at yk_device_upload, and yk_photon_build accepts it.
+ * YK_ERR_ARG unless samples >= 1; the other members are taken as the live
+ * object holds them. (FAST_TRIG's fCos answers exactly 1 for angles below
+ * about 0.02 degrees: such a sun has invpdf 0 and an infinite pdf and colPdf,
+ * as in the reference.) */
+int yk_scene_add_sun_light_state(yk_scene* s, const yk_sun_light_state* l);
+int yk_scene_get_sun_light_state(const yk_scene* s, int32_t i, yk_sun_light_state* out);
 /* constBackground_t (textureback.cc:187-218, "constant", ibl off): camera
  * rays that miss add color*power. rgb NULL removes the background. */
 int yk_scene_set_background(yk_scene* s, const float* rgb, float power);

@@ -207,6 +207,18 @@ struct SphereLightLayout : public light_t {
   unsigned int objID;
   float area, invArea;
 };
+// sunLight_t (sunlight.cc:27-50), private to its plugin's .cc file. Unverified
+// like the two above: this plugin is not compiled in this repository's setup.
+struct SunLightLayout : public light_t {
+  point3d_t worldCenter;
+  color_t color, colPdf;
+  vector3d_t direction, du, dv;
+  float pdf, invpdf;
+  double cosAngle;
+  int samples;
+  float worldRadius;
+  float ePdf;
+};
 // meshLight_t (meshlight.h:56-64) is declared in a header, but its members are
 // protected: read through YK_MEMBER like the area light's. Unverified: this
 // plugin is not compiled in this repository's setup.
@@ -392,6 +404,22 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
         }
         continue;
       }
+      if (tn == "N7yafaray10sunLight_tE") {
+        // photon maps included: worldCenter, worldRadius and ePdf are computed at upload from the scene bound
+        const SunLightLayout* sl = static_cast<const SunLightLayout*>(l);
+        yk_sun_light_state d{};
+        put3(d.color, sl->color.R, sl->color.G, sl->color.B);
+        put3(d.col_pdf, sl->colPdf.R, sl->colPdf.G, sl->colPdf.B);
+        put3(d.direction, sl->direction.x, sl->direction.y, sl->direction.z);
+        put3(d.du, sl->du.x, sl->du.y, sl->du.z);
+        put3(d.dv, sl->dv.x, sl->dv.y, sl->dv.z);
+        d.pdf = sl->pdf;
+        d.invpdf = sl->invpdf;
+        d.cos_angle = sl->cosAngle;
+        d.samples = sl->samples;
+        if (yk_scene_add_sun_light_state(ys, &d) != YK_OK) return fail();
+        continue;
+      }
       if (tn == "N7yafaray11meshLight_tE") {
         // yk_photon_build refuses it as well: its emitPhoton is not on the path
         if (params.integrator == YK_INTEGRATOR_PHOTON || params.caustic_type == YK_CAUSTIC_PHOTON ||
@@ -420,7 +448,7 @@ class gpuTiledIntegrator_t : public tiledIntegrator_t {
         continue;
       }
       areaLight_t* al = dynamic_cast<areaLight_t*>(l);
-      if (!al) return unsupported("only area, point, directional, spot, sphere and mesh lights run on the GPU path");
+      if (!al) return unsupported("only area, point, directional, spot, sphere, mesh and sun lights run on the GPU path");
       yk_area_light_state s{};
       const point3d_t& c = GET(*al, AlCorner);
       const vector3d_t &x = GET(*al, AlToX), &y = GET(*al, AlToY);

@@ -31,17 +31,25 @@ GL_ARITY = {"k_shade_primary": 4, "k_shade_bounce": 3, "k_path_start": 2, "k_fg_
             "k_photon_hit": 1, "k_pm_post": 1, "k_pm_finish": 1, "k_pt_caustic": 1, "k_spawn": 1}
 
 
+# kernels with a trailing light level XL after that (kXLNone 0 ... kXLSun 3), and their arity with it: a 0
+# is dropped first, so that the instantiations from before the argument keep their names
+XL_ARITY = {"k_fg_hit": 3, "k_photon_emit": 1}
+
+
 def short_name(mangled):
     dem = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip()
     name = re.sub(r"^void ", "", dem)
     name = re.sub(r"\(.*$", "", name.replace("(anonymous namespace)::", "")).replace("yk::", "")
     m = re.match(r"(\w+)<(.*)>$", name)
-    if m and m.group(1) in GL_ARITY:
+    if m and (m.group(1) in GL_ARITY or m.group(1) in XL_ARITY):
         args = [a.strip() for a in m.group(2).split(",")]
+        if len(args) == XL_ARITY.get(m.group(1)) and args[-1] == "0":
+            args.pop()
+            name = f"{m.group(1)}<{', '.join(args)}>" if args else m.group(1)
         # GL became a level (0 none, 1 glossy, 2 coated glossy): 0 and 1 print as the flag's false and true did
-        if len(args) == GL_ARITY[m.group(1)] and args[-1] in ("false", "0"):
+        if len(args) == GL_ARITY.get(m.group(1)) and args[-1] in ("false", "0"):
             name = f"{m.group(1)}<{', '.join(args[:-1])}>" if len(args) > 1 else m.group(1)
-        elif len(args) == GL_ARITY[m.group(1)] and args[-1] == "1":
+        elif len(args) == GL_ARITY.get(m.group(1)) and args[-1] == "1":
             name = f"{m.group(1)}<{', '.join(args[:-1] + ['true'])}>"
     return name
 
