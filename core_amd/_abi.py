@@ -16,6 +16,7 @@ YK_ERR_ABORTED = 7
 YK_ERR_ARG, YK_ERR_STATE, YK_ERR_HIP, YK_ERR_UNSUPPORTED, YK_ERR_ALLOC, YK_ERR_INTERNAL = 1, 2, 3, 4, 5, 6
 YK_MAT_SHINYDIFFUSE, YK_MAT_LIGHT, YK_MAT_GLOSSY = 0, 1, 2
 YK_MAT_COATED_GLOSSY = 4  # 3 is unassigned and refused
+YK_MAT_GLASS = 5
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_LIGHT_MESH = 5
 YK_LIGHT_SUN = 6
@@ -48,6 +49,14 @@ class yk_material(C.Structure):
                 ("diffuse_color", f3), ("glossy_reflect", C.c_float), ("exponent", C.c_float),
                 ("as_diffuse", C.c_int32), ("anisotropic", C.c_int32), ("exp_u", C.c_float),
                 ("exp_v", C.c_float)]
+
+
+class yk_glass_params(C.Structure):
+    _fields_ = [("filter_color", f3), ("fake_shadows", C.c_int32), ("dispersion_power", C.c_double)]
+
+
+class yk_glass_state(C.Structure):
+    _fields_ = [("filter_col", f3), ("fake_shadow", C.c_int32)]
 
 
 class yk_light(C.Structure):
@@ -237,6 +246,9 @@ SIGNATURES = {
     "yk_scene_create": (C.c_int, [C.POINTER(P)]),
     "yk_scene_destroy": (None, [P]),
     "yk_scene_add_material": (C.c_int, [P, C.POINTER(yk_material), i32p]),
+    "yk_scene_add_glass": (C.c_int, [P, C.POINTER(yk_material), C.POINTER(yk_glass_params), i32p]),
+    "yk_scene_add_glass_state": (C.c_int, [P, C.POINTER(yk_material_state), C.POINTER(yk_glass_state), i32p]),
+    "yk_scene_get_glass_state": (C.c_int, [P, i32, C.POINTER(yk_glass_state)]),
     "yk_scene_add_mesh": (C.c_int, [P, fp, i32, i32p, i32, i32, i32p]),
     "yk_scene_set_mesh_normals": (C.c_int, [P, i32, fp, i32, i32p, i32]),
     "yk_scene_set_mesh_base": (C.c_int, [P, i32]),

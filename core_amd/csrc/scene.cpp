@@ -149,6 +149,25 @@ yk_material_state material_state(const yk_material& m) {
   return o;
 }
 
+// glassMat_t::factory + ctor, glass.cc:55-69, 262-274 (no shader nodes, no dispersion, no absorption).
+// filt is the factory's double: filt*filtCol goes through color_t's operator*(CFLOAT, color_t), which
+// takes filt as a float, and color_t(1.f-filt) rounds the double difference to a float (color.h:41,64).
+yk_material_state glass_material_state(const yk_material& m, const yk_glass_params& g, yk_glass_state& gs) {
+  yk_material_state o{};
+  o.type = YK_MAT_GLASS;
+  const double filt = m.transmit_filter;
+  const float ff = (float)filt, rest = (float)(1.f - filt);
+  for (int k = 0; k < 3; ++k) {
+    gs.filter_col[k] = ff * g.filter_color[k] + rest;
+    o.mirror_color[k] = m.mirror_color[k];  // specRefCol
+  }
+  gs.fake_shadow = g.fake_shadows ? 1 : 0;
+  o.ior = (float)m.ior;  // glassMat_t(float IOR, ...)
+  o.bsdf_flags = kSpecular | kReflect | kTransmit;  // BSDF_ALL_SPECULAR
+  if (gs.fake_shadow) o.bsdf_flags |= kFilter;
+  return o;
+}
+
 yk_area_light_state light_state(const yk_light& l) {  // areaLight_t::factory + ctor, arealight.cc:30-49,171-192
   yk_area_light_state o{};
   const hv3 c = H(l.corner);
@@ -366,17 +385,27 @@ yk_camera_state camera_state(const yk_camera& c) {  // camera_t ctor + setAxis
   return o;
 }
 
-int Scene::add_material(const yk_material& m) {
+int Scene::add_material(const yk_material& m, const yk_glass_params* g) {
   materials.push_back(m);
   material_has_params.push_back(true);
-  material_states.push_back(material_state(m));
+  yk_glass_state gs{};
+  if (m.type == YK_MAT_GLASS) {
+    const yk_glass_params def{{1.f, 1.f, 1.f}, 0, 0.0};  // the factory's defaults
+    material_states.push_back(glass_material_state(m, g ? *g : def, gs));
+  } else {
+    material_states.push_back(material_state(m));
+  }
+  glass_states.push_back(gs);
   built = false;
   return (int)material_states.size() - 1;
 }
-int Scene::add_material_state(const yk_material_state& m) {
+int Scene::add_material_state(const yk_material_state& m, const yk_glass_state* g) {
   materials.push_back(yk_material{});
   material_has_params.push_back(false);
   material_states.push_back(m);
+  yk_glass_state gs{};
+  if (m.type == YK_MAT_GLASS) gs = g ? *g : yk_glass_state{{1.f, 1.f, 1.f}, 0};
+  glass_states.push_back(gs);
   built = false;
   return (int)material_states.size() - 1;
 }

@@ -60,6 +60,7 @@ struct Scene {
   bool camera_has_params = false;
   // ... and the reference object state the kernels consume
   std::vector<yk_material_state> material_states;
+  std::vector<yk_glass_state> glass_states;         // glass materials (zero entry for every other kind)
   std::vector<int> light_kind;                      // YK_LIGHT_*, scene light order
   std::vector<yk_area_light_state> light_states;    // area lights (zero entry for Dirac lights)
   std::vector<yk_dirac_light_state> dirac_states;   // point / directional (zero entry for area lights)
@@ -72,8 +73,8 @@ struct Scene {
   yk_camera_state camera_state{};
   bool has_camera = false;
 
-  int add_material(const yk_material& m);
-  int add_material_state(const yk_material_state& m);
+  int add_material(const yk_material& m, const yk_glass_params* g = nullptr);
+  int add_material_state(const yk_material_state& m, const yk_glass_state* g = nullptr);
   void add_light(const yk_light& l);
   void add_light_state(const yk_area_light_state& l);
   void add_dirac_light_state(const yk_dirac_light_state& l);
@@ -109,6 +110,8 @@ void gen_bumpy(Scene& s, int nu, int nv, int resx, int resy);
 // shinyDiffuseMat_t / lightMat_t factories, areaLight_t ctor (arealight.cc:30-49),
 // camera_t ctor + perspectiveCam_t::setAxis (camera.h:41-60, perspectiveCamera.cc:28-71).
 yk_material_state material_state(const yk_material& m);
+// glassMat_t factory + ctor (glass.cc:55-69, 262-274): the state and filterCol / fakeShadow beside it
+yk_material_state glass_material_state(const yk_material& m, const yk_glass_params& g, yk_glass_state& gs);
 yk_area_light_state light_state(const yk_light& l);
 yk_dirac_light_state dirac_state(const yk_light& l);
 // spotLight_t ctor (spotlight.cc:63-75), sphereLight_t ctor (spherelight.cc:64-72)

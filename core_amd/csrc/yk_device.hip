@@ -86,6 +86,12 @@ struct DMat {
       float mirror[3];    // mirror_color
       float ior;          // IOR
     } gl;
+    struct {  // glassMat_t (glass.cc:44-52) without nodes, dispersion or absorption; col above is unused
+      float filter[3];    // filterCol
+      float mirror[3];    // specRefCol
+      float ior;          // ior
+      int fake_shadow;    // fakeShadow: tmFlags is FILTER|TRANSMIT, else SPECULAR|TRANSMIT
+    } gs;
   };
   int on;             // mUseOrenNayar (shinydiffuse.cc:170-176) / glossyMat_t::orenNayar
   float on_a, on_b;   // mOrenNayar_A / mOrenNayar_B, orenA / orenB
@@ -449,10 +455,11 @@ __device__ __forceinline__ bool trav_begin(const DScene& S, Trav& st, const yk_r
 // (The reference's "exit == split" branch follows "exit <= split" and is
 // never taken, NaN included.)
 // Triangle test of one leaf entry; true when an any-hit query is done.
+template <bool GLT = false>
 __device__ __forceinline__ c3 mat_transparency(const DMat& M, const SurfPt& sp, v3 wo);
 __device__ __forceinline__ SurfPt make_surface(const DScene& S, v3 from, v3 dir, const yk_hit& h);
 
-template <bool CLOSEST, bool TS = false>
+template <bool CLOSEST, bool TS = false, bool GLT = false>
 __device__ __forceinline__ bool leaf_test(const DScene& S, Trav& st, uint32_t p, float4 A, float4 E1, float4 E2,
                                           bool& occluded) {
   float th, u, v;
@@ -478,7 +485,7 @@ __device__ __forceinline__ bool leaf_test(const DScene& S, Trav& st, uint32_t p,
         return true;
       }
       const SurfPt sp = make_surface(S, st.o, st.d, yk_hit{(int)p, th, u, v});
-      st.filt = cmul(st.filt, mat_transparency(M, sp, st.d));
+      st.filt = cmul(st.filt, mat_transparency<GLT>(M, sp, st.d));
       st.tdepth++;
       return false;
     }
@@ -499,7 +506,7 @@ __device__ __forceinline__ bool leaf_test(const DScene& S, Trav& st, uint32_t p,
 
 // Per-lane step (the transparent-shadow kernel, whose leaf body is
 // sequential: IntersectTS filters each transparent prim once, in leaf order).
-template <bool CLOSEST, bool TS = false, class STK = LaneStack>
+template <bool CLOSEST, bool TS = false, bool GLT = false, class STK = LaneStack>
 __device__ __forceinline__ bool trav_step(const DScene& S, Trav& st, const STK& stk, unsigned& nnodes,
                                           unsigned& ntris, bool& occluded) {
   if (st.dist < st.en_t) return true;
@@ -558,7 +565,7 @@ __device__ __forceinline__ bool trav_step(const DScene& S, Trav& st, const STK& 
     // load past the det test: a second dependent round trip per triangle)
     asm volatile("" : "+v"(A.x), "+v"(A.y), "+v"(A.z), "+v"(E1.x), "+v"(E1.y), "+v"(E1.z), "+v"(E2.x),
                  "+v"(E2.y), "+v"(E2.z));
-    if (leaf_test<CLOSEST, TS>(S, st, p, A, E1, E2, occluded)) return true;
+    if (leaf_test<CLOSEST, TS, GLT>(S, st, p, A, E1, E2, occluded)) return true;
   }
   if (CLOSEST && st.prim >= 0 && st.Z <= st.ex_t) return true;
   // pop: entry := exit, exit := previous exit
@@ -1189,7 +1196,7 @@ struct RaySrc {
 };
 
 template <bool CLOSEST, int NSEG, bool TS = false, bool BIG = false, bool UNI = false, int W = 1, bool SPLIT = false,
-          bool GROUP = false>
+          bool GROUP = false, bool GLT = false>
 __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned* __restrict__ idx,
                                            RayCount rc, yk_hit* __restrict__ hits, uint8_t* __restrict__ occl,
                                            unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,
@@ -1575,7 +1582,7 @@ __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned*
 #endif
     } else if (rid >= 0) {
       bool occ = false;
-      bool done = trav_step<CLOSEST, TS>(S, st, stk, nnodes, ntris, occ);
+      bool done = trav_step<CLOSEST, TS, GLT>(S, st, stk, nnodes, ntris, occ);
       if (runaway) {
         st.prim = -2;
         done = true;
@@ -1750,6 +1757,16 @@ k_trace_shadow_ts(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCou
                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
   trace_body<false, 1, true>(S, src, idx, n, nullptr, occl, work, ctr, ovf, ovf_depth, refill_min, tsf,
                                     ts_depth);
+}
+// the same for scenes that hold a glass with fake shadows: glassMat_t::getTransparency in the leaf body
+// (mat_transparency<true>); no other scene launches it
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5)))
+k_trace_shadow_ts_glass(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
+                        uint8_t* __restrict__ occl, float* __restrict__ tsf, int ts_depth,
+                        unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,
+                        uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
+  trace_body<false, 1, true, false, false, 1, false, false, true>(S, src, idx, n, nullptr, occl, work, ctr, ovf,
+                                                                  ovf_depth, refill_min, tsf, ts_depth);
 }
 // small scenes (traversal data in LDS, YK_SMALL_W waves per workgroup;
 // dynamic LDS = small_scene_bytes)
@@ -2367,6 +2384,135 @@ __device__ __forceinline__ void coated_specular(const DMat& M, const SurfPt& sp,
   refl = true;
 }
 
+// ---- glass (glassMat_t, glass.cc:28-337; refract(), vector3d.cc:86-108) ----
+// The dielectric without dispersion, absorption or shader nodes, in source
+// order like glossy and the coat: no reference output holds the material. Its
+// record is the gs half of DMat; eval is black and pdf is 0.
+
+// refract(), vector3d.cc:86-108: eta = 1.0/IOR is a double quotient stored to
+// float, k runs in float (integer literals), fSqrt is sqrtf
+__device__ __forceinline__ bool refract_ref(v3 n, v3 wi, v3& wo, float IOR) {
+  v3 N = n;
+  float eta = IOR;
+  const v3 I = vneg(wi);
+  float cos_v_n = vdot(wi, n);
+  if (cos_v_n < 0.f) {
+    N = vneg(n);
+    cos_v_n = -cos_v_n;
+  } else {
+    eta = (float)(1.0 / (double)IOR);
+  }
+  const float k = 1.f - eta * eta * (1.f - cos_v_n * cos_v_n);
+  if (k <= 0.f) return false;
+  const float f = eta * cos_v_n - sqrtf(k);
+  wo = vnormalize(V3(eta * I.x + f * N.x, eta * I.y + f * N.y, eta * I.z + f * N.z));
+  return true;
+}
+
+// the normal both sample() and getSpecular() use (glass.cc:93-96, 208-218): sp.N unless it disagrees with Ng
+// about wo's side, then bent just past wo's plane; 1.00001*cos_wo_N is a double product rounded to float where
+// it meets the vector, as in coated_specular
+__device__ __forceinline__ v3 glass_normal(const SurfPt& sp, v3 wo, bool& outside) {
+  outside = vdot(sp.Ng, wo) > 0.f;
+  const float cos_wo_N = vdot(sp.N, wo);
+  if (outside ? (cos_wo_N >= 0.f) : (cos_wo_N <= 0.f)) return sp.N;
+  const float f = (float)(1.00001 * (double)cos_wo_N);
+  return vnormalize(vsub(sp.N, vmul(f, wo)));
+}
+
+// glassMat_t::sample, glass.cc:84-188, the non-dispersive branch. ok = false
+// on the early return (the mask lacks BSDF_SPECULAR): pdf = 0, black, W and wi
+// untouched. The fall-through (a mask that matches neither pick) has set no wi
+// or W either and ends with pdf = 0. s.reverse is never set on this path.
+__device__ __forceinline__ c3 glass_sample(const DMat& M, const SurfPt& sp, v3 wo, v3& wi, float s1, unsigned flags,
+                                           float& pdf, float& W, bool& ok, unsigned& sflags) {
+  constexpr unsigned kSpec = BSDF_SPECULAR | BSDF_REFLECT;
+  if (!(flags & BSDF_SPECULAR)) {
+    pdf = 0.f;
+    ok = false;
+    return C3(0.f, 0.f, 0.f);
+  }
+  bool outside;
+  const v3 N = glass_normal(sp, wo, outside);
+  pdf = 1.f;
+  v3 refdir;
+  const float vn = 2.0f * vdot(wo, N);  // wi = wo; wi.reflect(N), vector3d.h:288-295
+  const v3 rdir = V3(vn * N.x - wo.x, vn * N.y - wo.y, vn * N.z - wo.z);
+  if (refract_ref(N, wo, refdir, M.gs.ior)) {
+    float Kr, Kt;
+    fresnel_ref(wo, N, M.gs.ior, Kr, Kt);
+    const float pKr = (float)(0.01 + 0.99 * (double)Kr), pKt = (float)(0.01 + 0.99 * (double)Kt);
+    const unsigned tm = M.gs.fake_shadow ? (BSDF_FILTER | BSDF_TRANSMIT) : (BSDF_SPECULAR | BSDF_TRANSMIT);
+    if (s1 < pKt && (flags & tm) == tm) {
+      wi = refdir;
+      pdf = pKt;
+      sflags = tm;
+      W = 1.f;
+      return C3(M.gs.filter[0], M.gs.filter[1], M.gs.filter[2]);
+    } else if ((flags & kSpec) == kSpec) {
+      wi = rdir;
+      pdf = pKr;
+      sflags = kSpec;
+      W = 1.f;
+      return C3(M.gs.mirror[0], M.gs.mirror[1], M.gs.mirror[2]);
+    }
+  } else if ((flags & kSpec) == kSpec) {  // total inner reflection: colour 1, pdf stays 1
+    wi = rdir;
+    sflags = kSpec;
+    W = 1.f;
+    return C3(1.f, 1.f, 1.f);
+  }
+  pdf = 0.f;
+  ok = false;
+  return C3(0.f, 0.f, 0.f);
+}
+
+// glassMat_t::getSpecular, glass.cc:204-253. raylevel is state.raylevel after
+// recursiveRaytrace's increment (1 at a camera hit): inside the glass the
+// Fresnel reflection is followed only below level 3.
+__device__ __forceinline__ void glass_specular(const DMat& M, const SurfPt& sp, v3 wo, int raylevel, bool& refl,
+                                               bool& refr, v3* dir, c3* col) {
+  bool outside;
+  const v3 N = glass_normal(sp, wo, outside);
+  const float vn = 2.0f * vdot(wo, N);
+  const v3 rdir = V3(vn * N.x - wo.x, vn * N.y - wo.y, vn * N.z - wo.z);
+  v3 refdir;
+  if (refract_ref(N, wo, refdir, M.gs.ior)) {
+    float Kr, Kt;
+    fresnel_ref(wo, N, M.gs.ior, Kr, Kt);
+    col[1] = C3(Kt * M.gs.filter[0], Kt * M.gs.filter[1], Kt * M.gs.filter[2]);
+    dir[1] = refdir;
+    refr = true;
+    if (outside || raylevel < 3) {
+      dir[0] = rdir;
+      col[0] = C3(Kr * M.gs.mirror[0], Kr * M.gs.mirror[1], Kr * M.gs.mirror[2]);
+      refl = true;
+    } else {
+      refl = false;
+    }
+  } else {  // total inner reflection
+    col[0] = C3(1.f, 1.f, 1.f);
+    dir[0] = rdir;
+    refl = true;
+    refr = false;
+  }
+}
+
+// glassMat_t::getTransparency, glass.cc:190-196
+__device__ __forceinline__ c3 glass_transparency(const DMat& M, const SurfPt& sp, v3 wo) {
+  float Kr, Kt;
+  fresnel_ref(wo, face_forward(sp.Ng, sp.N, wo), M.gs.ior, Kr, Kt);
+  return C3(Kt * M.gs.filter[0], Kt * M.gs.filter[1], Kt * M.gs.filter[2]);
+}
+
+// glassMat_t::getAlpha, glass.cc:198-202: 1.0 - energy() is a double difference stored to float;
+// energy() is (R+G+B)*0.333333f (color.h:77)
+__device__ __forceinline__ float glass_alpha(const DMat& M, const SurfPt& sp, v3 wo) {
+  const c3 t = glass_transparency(M, sp, wo);
+  const float alpha = (float)(1.0 - (double)((t.r + t.g + t.b) * 0.333333f));
+  return (alpha < 0.0f) ? 0.0f : alpha;
+}
+
 // shinyDiffuseMat_t::eval, shinydiffuse.cc:223-249 (compiled: cos_Ng_wl as
 // (y + z) + x; mD = ((1-c2)*c3)*mT), then mD *= OrenNayar(wo, wl, N) (:247).
 // ON = false: the scene has no Oren-Nayar material (the diffuse-only
@@ -2377,15 +2523,20 @@ __device__ __forceinline__ void coated_specular(const DMat& M, const SurfPt& sp,
 // GL is a level: kGLNone, kGLGlossy (1 in the instantiations' names), or
 // kGLCoated when the scene holds a coated glossy material as well or instead;
 // only then is the coat's code compiled in, so glossy-only scenes too run the
-// kernels they ran before.
-constexpr int kGLNone = 0, kGLGlossy = 1, kGLCoated = 2;
+// kernels they ran before. kGLGlass, on top of that, when the scene holds a
+// glass material: a glass record is recognised before any shinydiffuse member
+// (comp[], mirror[], mat_fresnel) is read, as the coat's is.
+constexpr int kGLNone = 0, kGLGlossy = 1, kGLCoated = 2, kGLGlass = 3;
 template <bool ON = true, int GL = kGLNone>
 __device__ __forceinline__ c3 mat_eval(const DMat& M, const SurfPt& sp, v3 wo, v3 wl) {
   if (M.type == YK_MAT_LIGHT) return C3(0.f, 0.f, 0.f);
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY) return glossy_eval(M, sp, wo, wl, BSDF_ALL);
-    if constexpr (GL == kGLCoated) {
+    if constexpr (GL >= kGLCoated) {
       if (M.type == YK_MAT_COATED_GLOSSY) return coated_eval(M, sp, wo, wl, BSDF_ALL);
+    }
+    if constexpr (GL >= kGLGlass) {
+      if (M.type == YK_MAT_GLASS) return C3(0.f, 0.f, 0.f);
     }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
@@ -2426,8 +2577,11 @@ __device__ __forceinline__ c3 mat_sample(const DMat& M, const SurfPt& sp, v3 wo,
   }
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY) return glossy_sample(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sflags);
-    if constexpr (GL == kGLCoated) {
+    if constexpr (GL >= kGLCoated) {
       if (M.type == YK_MAT_COATED_GLOSSY) return coated_sample(M, sp, wo, wi, s1in, s2in, flags, pdf, W, ok, sflags);
+    }
+    if constexpr (GL >= kGLGlass) {
+      if (M.type == YK_MAT_GLASS) return glass_sample(M, sp, wo, wi, s1in, flags, pdf, W, ok, sflags);
     }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
@@ -2546,9 +2700,12 @@ __device__ __forceinline__ float mat_pdf(const DMat& M, const SurfPt& sp, v3 wo,
   if constexpr (GL) {
     if (M.type == YK_MAT_GLOSSY)
       return glossy_pdf(M, sp, wo, wi, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
-    if constexpr (GL == kGLCoated) {
+    if constexpr (GL >= kGLCoated) {
       if (M.type == YK_MAT_COATED_GLOSSY)
         return coated_pdf(M, sp, wo, wi, BSDF_GLOSSY | BSDF_DIFFUSE | BSDF_DISPERSIVE | BSDF_REFLECT | BSDF_TRANSMIT);
+    }
+    if constexpr (GL >= kGLGlass) {
+      if (M.type == YK_MAT_GLASS) return 0.f;
     }
   }
   const float cos_Ng_wo = vdot(sp.Ng, wo);
@@ -2581,9 +2738,15 @@ __device__ __forceinline__ void mat_specular(const DMat& M, const SurfPt& sp, v3
                                              v3* dir, c3* col, int raylevel = 0) {
   refl = refr = false;
   if (M.type == YK_MAT_LIGHT) return;
-  if constexpr (GL == kGLCoated) {
+  if constexpr (GL >= kGLCoated) {
     if (M.type == YK_MAT_COATED_GLOSSY) {
       coated_specular(M, sp, wo, raylevel, refl, dir[0], col[0]);
+      return;
+    }
+  }
+  if constexpr (GL >= kGLGlass) {
+    if (M.type == YK_MAT_GLASS) {
+      glass_specular(M, sp, wo, raylevel, refl, refr, dir, col);
       return;
     }
   }
@@ -2617,7 +2780,12 @@ __device__ __forceinline__ void mat_specular(const DMat& M, const SurfPt& sp, v3
 // shinyDiffuseMat_t::getTransparency, shinydiffuse.cc:435-455 (only called on
 // transparent materials): accum = 1 - Kr*mirror; accum *= transparency*accum;
 // accum * (filter*diffuse + (1 - filter))
+// GLT: the scene holds a glass with fake shadows, whose getTransparency answers for its record.
+template <bool GLT>
 __device__ __forceinline__ c3 mat_transparency(const DMat& M, const SurfPt& sp, v3 wo) {
+  if constexpr (GLT) {
+    if (M.type == YK_MAT_GLASS) return glass_transparency(M, sp, wo);
+  }
   float accum = 1.f;
   const float Kr = mat_fresnel(M, wo, face_forward(sp.Ng, sp.N, wo));
   if (M.flags & BSDF_SPECULAR) accum = 1.f - Kr * M.comp[0];
@@ -4413,7 +4581,11 @@ __global__ void __launch_bounds__(256) k_spawn(DScene S, Batch B, RenderConst R,
   if (!(M.flags & (BSDF_SPECULAR | BSDF_FILTER))) return;
   const long long node = base + i;
   NS.flags[node] |= NF_SPEC;
-  if (R.integrator == YK_INTEGRATOR_PHOTON && (M.flags & BSDF_FILTER)) {
+  bool glass = false;
+  if constexpr (GL >= kGLGlass) glass = M.type == YK_MAT_GLASS;
+  if (glass) {  // glassMat_t::getAlpha, whether or not it fakes shadows
+    if (R.integrator == YK_INTEGRATOR_PHOTON) NS.malpha[node] = glass_alpha(M, sp, vneg(dir));
+  } else if (R.integrator == YK_INTEGRATOR_PHOTON && (M.flags & BSDF_FILTER)) {
     // shinyDiffuseMat_t::getAlpha (shinydiffuse.cc:457-469) of a transparent material
     const v3 wo = vneg(dir);
     const float Kr = mat_fresnel(M, wo, face_forward(sp.Ng, sp.N, wo));
@@ -5294,8 +5466,9 @@ constexpr TraceInfo kTrace[kTraceVariants] = {
 // material level (the kernels' DIFF and GL arguments, which exclude each
 // other: mat_sample) and its light level (XL), both fixed at upload.
 // kMatDiffuse: every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>);
-// kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated)
-enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kShadeMats };
+// kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated);
+// kMatGlass: one is glass (kGLGlass, which holds the glossy and coated code too)
+enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kMatGlass, kShadeMats };
 constexpr int kXLLevels = kXLSun + 1;
 struct ShadeVariant {
   int mat = kMatGeneral;  // ShadeMat
@@ -5340,9 +5513,9 @@ struct ShadeKernels {
 template <int MAT, int XL>
 constexpr ShadeKernels shade_cell() {
   constexpr bool DIFF = MAT == kMatDiffuse;
-  constexpr int GL = MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
+  constexpr int GL = MAT == kMatGlass ? kGLGlass : MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
   return {{k_shade_primary<DIFF, XL, false, GL>, k_shade_primary<DIFF, XL, true, GL>}, k_shade_bounce<DIFF, XL, GL>,
-          bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL == kGLCoated ? kGLCoated : kGLNone)>,
+          bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL >= kGLCoated ? GL : kGLNone)>,
           k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL, (XL == kXLSun ? kXLSun : kXLNone)>,
           k_photon_emit<(XL == kXLSun ? kXLSun : kXLNone)>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>,
           k_photon_hit<GL>};
@@ -5356,6 +5529,8 @@ constexpr ShadeKernels kShade[kShadeMats][kXLLevels] = {
      shade_cell<kMatGlossy, kXLSun>()},
     {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>(),
      shade_cell<kMatCoated, kXLSun>()},
+    {shade_cell<kMatGlass, kXLNone>(), shade_cell<kMatGlass, kXLSpotSphere>(), shade_cell<kMatGlass, kXLMesh>(),
+     shade_cell<kMatGlass, kXLSun>()},
 };
 // below the sun's level the table names no instantiation beyond those it named before: no glossy k_spawn, no
 // DIFF or XL where a kernel takes none; the sun's level adds k_fg_hit and k_photon_emit of its own
@@ -5369,6 +5544,15 @@ static_assert(kShade[kMatGlossy][kXLNone].spawn == kShade[kMatGeneral][kXLNone].
               kShade[kMatCoated][kXLSun].fg_hit != kShade[kMatCoated][kXLNone].fg_hit &&
               kShade[kMatDiffuse][kXLSun].photon_emit != kShade[kMatDiffuse][kXLNone].photon_emit &&
               kShade[kMatDiffuse][kXLSun].path_start == kShade[kMatDiffuse][kXLNone].path_start);
+// the glass row names kernels of its own wherever the coated row does, and the coated row names what it named before
+static_assert(kShade[kMatCoated][kXLNone].spawn == &k_spawn<kGLCoated> &&
+              kShade[kMatCoated][kXLNone].bounce == &k_shade_bounce<false, kXLNone, kGLCoated> &&
+              kShade[kMatCoated][kXLNone].photon_hit == &k_photon_hit<kGLCoated> &&
+              kShade[kMatGlass][kXLNone].spawn == &k_spawn<kGLGlass> &&
+              kShade[kMatGlass][kXLNone].bounce != kShade[kMatCoated][kXLNone].bounce &&
+              kShade[kMatGlass][kXLNone].photon_hit != kShade[kMatCoated][kXLNone].photon_hit &&
+              kShade[kMatGlass][kXLMesh].fg_hit == kShade[kMatGlass][kXLNone].fg_hit &&
+              kShade[kMatGlass][kXLMesh].photon_emit == kShade[kMatDiffuse][kXLNone].photon_emit);
 
 struct yk_device {
   int ordinal = 0;
@@ -5407,6 +5591,8 @@ struct yk_device {
   int refill = 24;  // idle lanes before a traversal wave refills (set_handout)
   int refill_shadow = 24;  // the same for the any-hit kernels
   int per_cu_ts = 1;
+  int per_cu_ts_glass = 1;  // k_trace_shadow_ts_glass
+  bool ts_glass = false;    // the scene holds a glass with fake shadows: transparent shadows run k_trace_shadow_ts_glass
   int per_cu_lookup[2] = {1, 1};  // k_pm_lookup<false / true> resident waves per CU
   // node store of the specular recursion (k_finish_spec / k_spawn / k_fold)
   DBuf<float> nE, nD, nP, nrcol, nalpha, nmalpha;
@@ -5752,7 +5938,7 @@ void directional_photon_frame(DLight& D, const float* bound) {
   }
 }
 
-DMat make_mat(const yk_material_state& m) {
+DMat make_mat(const yk_material_state& m, const yk_glass_state& g) {
   DMat M{};
   M.type = m.type;
   M.flags = m.bsdf_flags;
@@ -5764,6 +5950,15 @@ DMat make_mat(const yk_material_state& m) {
   M.on = m.oren_nayar ? 1 : 0;
   M.on_a = m.oren_nayar_a;
   M.on_b = m.oren_nayar_b;
+  if (m.type == YK_MAT_GLASS) {
+    for (int k = 0; k < 3; ++k) {
+      M.gs.filter[k] = g.filter_col[k];
+      M.gs.mirror[k] = m.mirror_color[k];
+    }
+    M.gs.ior = m.ior;
+    M.gs.fake_shadow = g.fake_shadow ? 1 : 0;
+    return M;
+  }
   if (m.type == YK_MAT_GLOSSY || m.type == YK_MAT_COATED_GLOSSY) {
     for (int k = 0; k < 3; ++k) {
       M.col[k] = m.gloss_color[k];
@@ -5993,12 +6188,12 @@ void enqueue_trace(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayC
 void enqueue_trace_ts(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayCount n, uint8_t* occ,
                       float* filt, int max_depth, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0,
                       hipEvent_t ev1) {
-  const long long grid = (long long)d->cus * d->per_cu_ts;
+  const long long grid = (long long)d->cus * (d->ts_glass ? d->per_cu_ts_glass : d->per_cu_ts);
   const int ovf_depth = std::max(1, stack_depth(d) - kStackLds);
   P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64);
   if (ev0) HIPCHK(hipEventRecord(ev0, P.stream));
-  launch(k_trace_shadow_ts, (unsigned)grid, 64, 0, P.stream, d->S, rays, idx, n, occ, filt, max_depth, work, acc,
-         P.ovf.p, ovf_depth, d->refill_shadow);
+  launch(d->ts_glass ? k_trace_shadow_ts_glass : k_trace_shadow_ts, (unsigned)grid, 64, 0, P.stream, d->S, rays, idx, n,
+         occ, filt, max_depth, work, acc, P.ovf.p, ovf_depth, d->refill_shadow);
   if (ev1) HIPCHK(hipEventRecord(ev1, P.stream));
 }
 
@@ -6192,6 +6387,8 @@ int yk_device_open(int32_t ordinal, yk_device** out) {
   int blocks = 0;
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_ts, 64, 0));
   d->per_cu_ts = std::max(1, blocks);
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_trace_shadow_ts_glass, 64, 0));
+  d->per_cu_ts_glass = std::max(1, blocks);
   HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, k_pm_lookup<false>, 64, 0));
   d->per_cu_lookup[0] = std::max(1, blocks);
   if (const char* v = std::getenv("YK_VERBOSE"); v && std::atoi(v) > 0)
@@ -6304,18 +6501,21 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   std::vector<DMat> mats;
   d->spec = false;
   d->mat_flags.clear();
-  for (const auto& m : S.material_states) {
-    mats.push_back(make_mat(m));
+  d->ts_glass = false;
+  for (size_t i = 0; i < S.material_states.size(); ++i) {
+    const auto& m = S.material_states[i];
+    mats.push_back(make_mat(m, S.glass_states[i]));
     d->mat_flags.push_back(m.bsdf_flags);
     if (m.bsdf_flags & (BSDF_SPECULAR | BSDF_FILTER)) d->spec = true;
+    if (m.type == YK_MAT_GLASS && S.glass_states[i].fake_shadow) d->ts_glass = true;
   }
   {  // the scene's material level: the highest any material needs; YK_DIFF=0: never the diffuse-only one
     const char* e = std::getenv("YK_DIFF");
     int mat = (e && std::atoi(e) == 0) ? kMatGeneral : kMatDiffuse;
     for (const DMat& m : mats) {
       const bool diff = m.type == YK_MAT_LIGHT || (m.ncomp == 1 && m.cflags[0] == (BSDF_DIFFUSE | BSDF_REFLECT) && !m.on);
-      mat = std::max<int>(mat, m.type == YK_MAT_COATED_GLOSSY ? kMatCoated : m.type == YK_MAT_GLOSSY ? kMatGlossy
-                               : diff ? kMatDiffuse : kMatGeneral);
+      mat = std::max<int>(mat, m.type == YK_MAT_GLASS ? kMatGlass : m.type == YK_MAT_COATED_GLOSSY ? kMatCoated
+                               : m.type == YK_MAT_GLOSSY ? kMatGlossy : diff ? kMatDiffuse : kMatGeneral);
     }
     d->shade.mat = mat;
   }

@@ -55,8 +55,24 @@ namespace {
 bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 }  // namespace
 
+int yk_scene_add_glass(yk_scene* s, const yk_material* m, const yk_glass_params* g, int32_t* id_out) {
+  if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_glass: NULL argument");
+  if (m->type != YK_MAT_GLASS) return set_error(YK_ERR_ARG, "yk_scene_add_glass: the material's type must be YK_MAT_GLASS");
+  if (!finite3(m->mirror_color) || !std::isfinite(m->ior) || !std::isfinite(m->transmit_filter) ||
+      (g && (!finite3(g->filter_color) || std::isnan(g->dispersion_power))))
+    return set_error(YK_ERR_ARG, "yk_scene_add_glass: glass colours, transmit_filter, IOR and dispersion_power must be finite");
+  if (g && g->dispersion_power > 0.0)
+    return set_error(YK_ERR_UNSUPPORTED, "glass with dispersion_power > 0 (BSDF_DISPERSIVE) is not on the GPU path");
+  YK_GUARD_BEGIN
+  const int id = s->s.add_material(*m, g);
+  if (id_out) *id_out = id;
+  return YK_OK;
+  YK_GUARD_END
+}
+
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material: NULL argument");
+  if (m->type == YK_MAT_GLASS) return yk_scene_add_glass(s, m, nullptr, id_out);
   if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY &&
       m->type != YK_MAT_COATED_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");
@@ -86,8 +102,40 @@ int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out) {
   YK_GUARD_END
 }
 
+int yk_scene_add_glass_state(yk_scene* s, const yk_material_state* m, const yk_glass_state* g, int32_t* id_out) {
+  if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_glass_state: NULL argument");
+  if (m->type != YK_MAT_GLASS)
+    return set_error(YK_ERR_ARG, "yk_scene_add_glass_state: the state's type must be YK_MAT_GLASS");
+  if (!finite3(m->mirror_color) || !std::isfinite(m->ior) || (g && !finite3(g->filter_col)))
+    return set_error(YK_ERR_ARG, "yk_scene_add_glass_state: glass colours and IOR must be finite");
+  // BSDF_DISPERSIVE (dispersion_power > 0) and BSDF_VOLUMETRIC ("absorption": the beer volume handler)
+  if (m->bsdf_flags & (0x8u | 0x100u))
+    return set_error(YK_ERR_UNSUPPORTED, "glass with dispersion or absorption (BSDF_DISPERSIVE, BSDF_VOLUMETRIC) is not on the GPU path");
+  // glass.cc:60-61. The device record keeps glass's members over shinydiffuse's, so no other flag may steer a kernel there.
+  const bool fake = g && g->fake_shadow;
+  if ((g && g->fake_shadow != 0 && g->fake_shadow != 1) || m->bsdf_flags != ((0x1u | 0x10u | 0x20u) | (fake ? 0x40u : 0u)))
+    return set_error(YK_ERR_ARG,
+                     "yk_scene_add_glass_state: a glass state's bsdf_flags must be BSDF_SPECULAR | BSDF_REFLECT | "
+                     "BSDF_TRANSMIT, with BSDF_FILTER if and only if fake_shadow is 1");
+  YK_GUARD_BEGIN
+  const int id = s->s.add_material_state(*m, g);
+  if (id_out) *id_out = id;
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_glass_state(const yk_scene* s, int32_t i, yk_glass_state* out) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.material_states.size())
+    return set_error(YK_ERR_ARG, "yk_scene_get_glass_state: bad arguments");
+  if (s->s.material_states[i].type != YK_MAT_GLASS)
+    return set_error(YK_ERR_STATE, "yk_scene_get_glass_state: material is not a glass");
+  *out = s->s.glass_states[i];
+  return YK_OK;
+}
+
 int yk_scene_add_material_state(yk_scene* s, const yk_material_state* m, int32_t* id_out) {
   if (!s || !m) return set_error(YK_ERR_ARG, "yk_scene_add_material_state: NULL argument");
+  if (m->type == YK_MAT_GLASS) return yk_scene_add_glass_state(s, m, nullptr, id_out);
   if (m->type != YK_MAT_SHINYDIFFUSE && m->type != YK_MAT_LIGHT && m->type != YK_MAT_GLOSSY &&
       m->type != YK_MAT_COATED_GLOSSY)
     return set_error(YK_ERR_UNSUPPORTED, "material type not supported by the GPU path");

@@ -161,6 +161,7 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
   if (fn == YK_MATERIAL_PROBE_EVAL) {
     const c3 col = M.type == YK_MAT_GLOSSY          ? glossy_eval(M, sp, wo, ld3(x + 6), flags)
                    : M.type == YK_MAT_COATED_GLOSSY ? coated_eval(M, sp, wo, ld3(x + 6), flags)
+                   : M.type == YK_MAT_GLASS         ? mat_eval<true, kGLGlass>(M, sp, wo, ld3(x + 6))
                                                     : mat_eval(M, sp, wo, ld3(x + 6));
     o[0] = col.r;
     o[1] = col.g;
@@ -170,7 +171,7 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
     float pdf = 0.f, W = 0.f;
     bool ok;
     unsigned sfl;
-    const c3 col = mat_sample<false, kGLCoated>(M, sp, wo, wi, x[6], x[7], flags, pdf, W, ok, sfl);
+    const c3 col = mat_sample<false, kGLGlass>(M, sp, wo, wi, x[6], x[7], flags, pdf, W, ok, sfl);
     o[0] = ok ? 1.f : 0.f;
     o[1] = wi.x;
     o[2] = wi.y;
@@ -185,23 +186,37 @@ __global__ void k_material_probe(int mi, int fn, const float* in, long long n, f
     bool refl, refr;
     v3 dir[2] = {V3(0.f, 0.f, 0.f), V3(0.f, 0.f, 0.f)};
     c3 col[2] = {C3(0.f, 0.f, 0.f), C3(0.f, 0.f, 0.f)};
-    mat_specular<kGLCoated>(M, sp, wo, refl, refr, dir, col, (int)x[9]);
-    o[0] = refl ? 1.f : 0.f;
-    o[1] = dir[0].x;
-    o[2] = dir[0].y;
-    o[3] = dir[0].z;
-    o[4] = col[0].r;
-    o[5] = col[0].g;
-    o[6] = col[0].b;
+    mat_specular<kGLGlass>(M, sp, wo, refl, refr, dir, col, (int)x[9]);
+    // a glass with in[8] == 1: the refraction child in the reflection's slots, and the reflection's flag behind it
+    const int k = (M.type == YK_MAT_GLASS && x[8] == 1.f) ? 1 : 0;
+    o[0] = (k ? refr : refl) ? 1.f : 0.f;
+    o[1] = k ? dir[1].x : dir[0].x;
+    o[2] = k ? dir[1].y : dir[0].y;
+    o[3] = k ? dir[1].z : dir[0].z;
+    o[4] = k ? col[1].r : col[0].r;
+    o[5] = k ? col[1].g : col[0].g;
+    o[6] = k ? col[1].b : col[0].b;
+    if (M.type == YK_MAT_GLASS) o[7] = (k ? refl : refr) ? 1.f : 0.f;
     if (M.type == YK_MAT_COATED_GLOSSY) {  // fresnel() on its own, at the face-forwarded normal
       float Kr, Kt;
       fresnel_ref(wo, face_forward(sp.Ng, sp.N, wo), M.gl.ior, Kr, Kt);
       o[7] = Kr;
       o[8] = Kt;
     }
+  } else if (fn == YK_MATERIAL_PROBE_TRANSPARENCY) {
+    // glossy and coated records have no getTransparency and lie over the shinydiffuse members: zeros
+    if (M.type == YK_MAT_SHINYDIFFUSE || M.type == YK_MAT_GLASS) {
+      const c3 col = mat_transparency<true>(M, sp, wo);
+      o[0] = col.r;
+      o[1] = col.g;
+      o[2] = col.b;
+    }
+  } else if (fn == YK_MATERIAL_PROBE_ALPHA) {
+    if (M.type == YK_MAT_GLASS) o[0] = glass_alpha(M, sp, wo);
   } else {
     o[0] = M.type == YK_MAT_GLOSSY          ? glossy_pdf(M, sp, wo, ld3(x + 6), flags)
            : M.type == YK_MAT_COATED_GLOSSY ? coated_pdf(M, sp, wo, ld3(x + 6), flags)
+           : M.type == YK_MAT_GLASS         ? mat_pdf<kGLGlass>(M, sp, wo, ld3(x + 6))
                                             : mat_pdf(M, sp, wo, ld3(x + 6));
   }
 }
@@ -257,7 +272,7 @@ extern "C" int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t 
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_material_probe: no scene uploaded");
   if (mat_index < 0 || mat_index >= (int32_t)d->mats_host.size())
     return set_error(YK_ERR_ARG, "yk_debug_material_probe: no such material");
-  if (fn < YK_MATERIAL_PROBE_EVAL || fn > YK_MATERIAL_PROBE_SPECULAR)
+  if (fn < YK_MATERIAL_PROBE_EVAL || fn > YK_MATERIAL_PROBE_ALPHA)
     return set_error(YK_ERR_ARG, "yk_debug_material_probe: unknown function");
   if (n == 0) return YK_OK;
   YK_GUARD_BEGIN

@@ -33,9 +33,10 @@ class Scene:
     # -- assembly ------------------------------------------------------
     def add_material(self, type_=A.YK_MAT_SHINYDIFFUSE, color=(1, 1, 1), diffuse_reflect=None, emit=0.0,
                      power=1.0, double_sided=False, mirror_color=(1, 1, 1), specular_reflect=0.0,
-                     transparency=0.0, translucency=0.0, transmit_filter=1.0, fresnel_effect=False, ior=None,
+                     transparency=0.0, translucency=0.0, transmit_filter=None, fresnel_effect=False, ior=None,
                      diffuse_brdf="lambert", sigma=0.1, diffuse_color=(1, 1, 1), glossy_reflect=1.0,
-                     exponent=50.0, as_diffuse=True, anisotropic=False, exp_u=50.0, exp_v=50.0):
+                     exponent=50.0, as_diffuse=True, anisotropic=False, exp_u=50.0, exp_v=50.0,
+                     filter_color=(1, 1, 1), fake_shadows=False, dispersion_power=0.0):
         """shinydiffusemat / light_mat parameters with the reference factory defaults
         (shinydiffuse.cc:474-514, simple.cc:80-90); diffuse_brdf "oren_nayar"
         with roughness sigma (shinydiffuse.cc:505-514).
@@ -44,18 +45,27 @@ class Scene:
         diffuse_color, glossy_reflect, exponent, as_diffuse, anisotropic, exp_u, exp_v
         are its own; "Oren-Nayar" is accepted as the reference spells it for this kind.
         type_ = A.YK_MAT_COATED_GLOSSY: coated_glossy (coatedglossy.cc:420-498) -- the glossy
-        keywords plus mirror_color and ior, which defaults to 1.4 for it (1.33 otherwise)."""
+        keywords plus mirror_color and ior, which defaults to 1.4 for it (1.33 otherwise).
+        type_ = A.YK_MAT_GLASS: glass (glass.cc:260-337) -- ior (default 1.4), mirror_color,
+        transmit_filter (default 0 for it) and its own filter_color, fake_shadows and
+        dispersion_power, which must be 0 (dispersion is not on the GPU path)."""
         brdf = {"lambert": A.YK_BRDF_LAMBERT, "oren_nayar": A.YK_BRDF_OREN_NAYAR,
                 "Oren-Nayar": A.YK_BRDF_OREN_NAYAR}[diffuse_brdf]
         if diffuse_reflect is None:
             diffuse_reflect = 0.0 if type_ in (A.YK_MAT_GLOSSY, A.YK_MAT_COATED_GLOSSY) else 1.0
         if ior is None:
-            ior = 1.4 if type_ == A.YK_MAT_COATED_GLOSSY else 1.33
+            ior = 1.4 if type_ in (A.YK_MAT_COATED_GLOSSY, A.YK_MAT_GLASS) else 1.33
+        if transmit_filter is None:
+            transmit_filter = 0.0 if type_ == A.YK_MAT_GLASS else 1.0
         m = A.yk_material(type_, A.f3(*color), diffuse_reflect, emit, power, int(double_sided),
                           A.f3(*mirror_color), specular_reflect, transparency, translucency, transmit_filter,
                           int(fresnel_effect), ior, brdf, sigma, A.f3(*diffuse_color), glossy_reflect, exponent,
                           int(as_diffuse), int(anisotropic), exp_u, exp_v)
         mid = C.c_int32()
+        if type_ == A.YK_MAT_GLASS:
+            g = A.yk_glass_params(A.f3(*filter_color), int(fake_shadows), dispersion_power)
+            A.check(A.lib().yk_scene_add_glass(self._p, C.byref(m), C.byref(g), C.byref(mid)))
+            return mid.value
         A.check(A.lib().yk_scene_add_material(self._p, C.byref(m), C.byref(mid)))
         return mid.value
 
@@ -203,10 +213,19 @@ class Scene:
         return p
 
     # -- reference object state (what a plugin reads from live objects) ---
-    def add_material_state(self, st):
+    def add_material_state(self, st, glass=None):
+        """glass: the yk_glass_state of a YK_MAT_GLASS state (filterCol, fakeShadow)"""
         mid = C.c_int32()
+        if glass is not None:
+            A.check(A.lib().yk_scene_add_glass_state(self._p, C.byref(st), C.byref(glass), C.byref(mid)))
+            return mid.value
         A.check(A.lib().yk_scene_add_material_state(self._p, C.byref(st), C.byref(mid)))
         return mid.value
+
+    def glass_state(self, i):
+        g = A.yk_glass_state()
+        A.check(A.lib().yk_scene_get_glass_state(self._p, i, C.byref(g)))
+        return g
 
     def add_area_light_state(self, st):
         A.check(A.lib().yk_scene_add_area_light_state(self._p, C.byref(st)))

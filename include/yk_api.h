@@ -43,7 +43,7 @@ extern "C" {
 
 /* Value 3 is unassigned and stays refused (YK_ERR_UNSUPPORTED): callers and
  * tests rely on it as "a type the path does not know". */
-enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1, YK_MAT_GLOSSY = 2, YK_MAT_COATED_GLOSSY = 4 };
+enum { YK_MAT_SHINYDIFFUSE = 0, YK_MAT_LIGHT = 1, YK_MAT_GLOSSY = 2, YK_MAT_COATED_GLOSSY = 4, YK_MAT_GLASS = 5 };
 typedef struct yk_material {
   int32_t type;           /* YK_MAT_*                                               */
   float color[3];         /* "color"  shinydiffuse.cc:474,483 / simple.cc:82        */
@@ -89,7 +89,22 @@ typedef struct yk_material {
    * factory's `if(ior == 1.f) ior = 1.0000001f` is applied as written (the
    * double compared with and assigned a float literal, then held as a float).
    * as_diffuse == 0 is YK_ERR_UNSUPPORTED here too. */
+  /* glass (glassMat_t::factory, glass.cc:260-337) reads `ior` ("IOR" [1.4 for
+   * this kind]), `mirror_color` ("mirror_color" [1,1,1]) and `transmit_filter`
+   * ("transmit_filter" [0 for this kind]) from this struct, whose size and
+   * offsets callers have pinned; its own parameters travel in yk_glass_params. */
 } yk_material;
+/* glassMat_t's own parameters, beside a yk_material of type YK_MAT_GLASS
+ * (yk_scene_add_glass). There is no absorption field: "absorption" makes the
+ * reference attach the beer volume handler (BSDF_VOLUMETRIC), which the GPU
+ * path does not have, so a host plugin must refuse such a material itself.
+ * dispersion_power > 0 (BSDF_DISPERSIVE: state.chromatic, wavelengths) is
+ * YK_ERR_UNSUPPORTED. Shader nodes and bump stay out, as for every kind. */
+typedef struct yk_glass_params {
+  float filter_color[3];   /* "filter_color" [1,1,1]                                 */
+  int32_t fake_shadows;    /* "fake_shadows" [0]: isTransparent(), BSDF_FILTER       */
+  double dispersion_power; /* "dispersion_power" [0], parsed as double               */
+} yk_glass_params;
 enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 
 /* YK_LIGHT_MESH is the kind yk_scene_get_light and the device state report for
@@ -365,6 +380,12 @@ void yk_scene_destroy(yk_scene* s);
  * a coated state whose bsdf_flags, ncomp and comp_flags are not what
  * coatedglossy.cc:84-101 computes (see yk_material_state). */
 int yk_scene_add_material(yk_scene* s, const yk_material* m, int32_t* id_out);
+/* A glass material: m->type must be YK_MAT_GLASS, g its own parameters (NULL:
+ * the factory defaults, which is also what yk_scene_add_material gives a
+ * YK_MAT_GLASS). Runs glassMat_t's factory and constructor as written
+ * (glass.cc:55-69, 262-274). YK_ERR_ARG for a non-finite colour, IOR or
+ * transmit_filter; YK_ERR_UNSUPPORTED for dispersion_power > 0. */
+int yk_scene_add_glass(yk_scene* s, const yk_material* m, const yk_glass_params* g, int32_t* id_out);
 /* one TRIM mesh: points xyz (npoints*3), faces abc (nfaces*3); startTriMesh +
  * addVertex* + addTriangle* + endTriMesh (scene.cc:265-320,520-625) */
 int yk_scene_add_mesh(yk_scene* s, const float* points, int32_t npoints, const int32_t* faces,
@@ -500,7 +521,18 @@ typedef struct yk_material_state {
    * cFlags {SPECULAR|REFLECT, DIFFUSE|REFLECT, DIFFUSE|REFLECT or BSDF_NONE};
    * anything else is YK_ERR_ARG. */
   float ior;
+  /* A YK_MAT_GLASS state (glassMat_t, glass.cc:44-52) holds specRefCol in
+   * mirror_color and the member ior in `ior`; filterCol and fakeShadow travel in
+   * yk_glass_state (yk_scene_add_glass_state), since this struct's size is
+   * pinned by its callers. bsdf_flags must be exactly BSDF_SPECULAR |
+   * BSDF_REFLECT | BSDF_TRANSMIT, with BSDF_FILTER if and only if fake_shadow is
+   * set (YK_ERR_ARG otherwise; BSDF_DISPERSIVE or BSDF_VOLUMETRIC:
+   * YK_ERR_UNSUPPORTED); tmFlags follows from fake_shadow. */
 } yk_material_state;
+typedef struct yk_glass_state {
+  float filter_col[3];      /* filterCol = filt*filter_color + color_t(1.f - filt)      */
+  int32_t fake_shadow;      /* fakeShadow                                                */
+} yk_glass_state;
 
 typedef struct yk_area_light_state { /* areaLight_t members (arealight.h:45-53) */
   float corner[3], to_x[3], to_y[3];
@@ -578,6 +610,15 @@ typedef struct yk_camera_state { /* the camera after its ctor and setAxis (persp
 } yk_camera_state;
 
 int yk_scene_add_material_state(yk_scene* s, const yk_material_state* m, int32_t* id_out);
+/* A YK_MAT_GLASS state with its filterCol and fakeShadow (g NULL: filterCol 1,
+ * no fake shadows, which is also what yk_scene_add_material_state gives a
+ * glass state). So a glass with fake shadows, whose bsdf_flags carry
+ * BSDF_FILTER, is YK_ERR_ARG through yk_scene_add_material_state and
+ * round-trips through this pair only: yk_scene_get_material_state plus
+ * yk_scene_get_glass_state, then yk_scene_add_glass_state.
+ * yk_scene_get_glass_state: YK_ERR_STATE when material i is of another kind. */
+int yk_scene_add_glass_state(yk_scene* s, const yk_material_state* m, const yk_glass_state* g, int32_t* id_out);
+int yk_scene_get_glass_state(const yk_scene* s, int32_t i, yk_glass_state* out);
 int yk_scene_add_area_light_state(yk_scene* s, const yk_area_light_state* l);
 /* point / directional light (light_t::diracLight() == true): one shadow ray
  * per estimate, mcintegrator.cc:85-100 */

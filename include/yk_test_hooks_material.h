@@ -11,7 +11,7 @@ extern "C" {
 
 /* Runs, in a kernel on `d`, the device functions the shading kernels call for
  * material `mat_index` of the resident scene (shinydiffuse, light_mat or
- * glossy or coated glossy) at a flat surface point, over n host-supplied inputs. Every input
+ * glossy, coated glossy or glass) at a flat surface point, over n host-supplied inputs. Every input
  * is YK_MATERIAL_PROBE_IN floats, every output YK_MATERIAL_PROBE_OUT floats,
  * zero where nothing is listed. The surface point is sp.Ng = sp.N = N; its
  * tangents are createCS(N) when in[19] is 0, and NU = in[13..15],
@@ -31,11 +31,22 @@ extern "C" {
  *           -> refl[0], dir[1..3], col[4..6] of the material's getSpecular
  *           reflection (zero where it reflects nothing); for a coated glossy
  *           material also fresnel()'s Kr[7], Kt[8] at FACE_FORWARD(Ng, N, wo)
+ *           For a glass material in[8] chooses the child: 0 the reflection as
+ *           above, 1 the refraction, refr[0], dir[1..3], col[4..6]; [7] is then
+ *           the other child's flag (refr beside the reflection, refl beside
+ *           the refraction)
+ *   TRANSPARENCY in: N[0..2], wo[3..5] -> getTransparency(sp, wo)[0..2] of a
+ *           shinydiffuse or glass material (the transparent-shadow leaf body);
+ *           zero for every other kind
+ *   ALPHA   in: N[0..2], wo[3..5] -> a glass material's getAlpha[0]; 0 for
+ *           every other kind
+ * For a glass material EVAL gives black and PDF 0, and SAMPLE reads s1 only.
  * FPOW and ATAN_TAN read no material; mat_index must still be valid.
  * With in[19] == 2 the tangents are given as above and the geometric normal
  * is sp.Ng = in[10..12], so that N and Ng can disagree about wo's side. */
 enum { YK_MATERIAL_PROBE_EVAL = 0, YK_MATERIAL_PROBE_SAMPLE = 1, YK_MATERIAL_PROBE_PDF = 2,
-       YK_MATERIAL_PROBE_FPOW = 3, YK_MATERIAL_PROBE_ATAN_TAN = 4, YK_MATERIAL_PROBE_SPECULAR = 5 };
+       YK_MATERIAL_PROBE_FPOW = 3, YK_MATERIAL_PROBE_ATAN_TAN = 4, YK_MATERIAL_PROBE_SPECULAR = 5,
+       YK_MATERIAL_PROBE_TRANSPARENCY = 6, YK_MATERIAL_PROBE_ALPHA = 7 };
 enum { YK_MATERIAL_PROBE_IN = 20, YK_MATERIAL_PROBE_OUT = 10 };
 int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t fn, const float* in, int64_t n, float* out);
 

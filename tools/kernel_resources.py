@@ -7,7 +7,7 @@ flags. No GPU is needed.
   tools/kernel_resources.py diff OLD NEW      compare two saved tables
 
 Kernel names are demangled, and the trailing template argument GL (the scene's
-glossy level: kGLNone 0, kGLGlossy 1, kGLCoated 2) is listed the way the
+glossy level: kGLNone 0, kGLGlossy 1, kGLCoated 2, kGLGlass 3) is listed the way the
 tables in profiles/ have listed it since it was a flag: dropped where it is 0
 (or `false`), its default, and `true` where it is 1. The table lists
 k_shade_primary<false, 0, false, 0> as k_shade_primary<false, 0, false>,
