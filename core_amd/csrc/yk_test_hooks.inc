@@ -13,6 +13,10 @@ bool debug_hooks_on() {
   const char* e = std::getenv("YK_DEBUG_HOOKS");
   return e && e[0] == '1';
 }
+// the refusal every entry point opens with, under the entry point's own name
+#define YK_HOOK_ONLY \
+  if (!debug_hooks_on()) \
+  return set_error(YK_ERR_UNSUPPORTED, std::string(__func__) + ": test hook disabled (YK_DEBUG_HOOKS=1)")
 
 __global__ void k_qmc_probe(int fn, const void* in, const uint32_t* in2, long long n, void* out) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -235,8 +239,7 @@ __global__ void k_camera_probe(const float* in, long long n, yk_ray* rays, float
 }  // namespace
 
 extern "C" int yk_debug_camera_rays(yk_device* d, const float* pxy_lens, int64_t n, yk_ray* rays_out, float* wt_out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_camera_rays: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !pxy_lens || !rays_out || !wt_out || n < 0 || n > (1ll << 24))
     return set_error(YK_ERR_ARG, "yk_debug_camera_rays: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_camera_rays: no scene uploaded");
@@ -265,8 +268,7 @@ extern "C" int yk_debug_camera_rays(yk_device* d, const float* pxy_lens, int64_t
 
 extern "C" int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t fn, const float* in, int64_t n,
                                        float* out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_material_probe: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !in || !out || n < 0 || n > (1ll << 24))
     return set_error(YK_ERR_ARG, "yk_debug_material_probe: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_material_probe: no scene uploaded");
@@ -293,8 +295,7 @@ extern "C" int yk_debug_material_probe(yk_device* d, int32_t mat_index, int32_t 
 
 extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t fn, const float* in, int64_t n,
                                     float* out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_light_probe: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !in || !out || n < 0 || n > (1ll << 24)) return set_error(YK_ERR_ARG, "yk_debug_light_probe: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_light_probe: no scene uploaded");
   if (light_index < 0 || light_index >= d->nlights)
@@ -326,8 +327,7 @@ extern "C" int yk_debug_light_probe(yk_device* d, int32_t light_index, int32_t f
 
 extern "C" int yk_debug_qmc_probe(yk_device* d, int32_t fn, const void* in, const uint32_t* in2, int64_t n,
                                   void* out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_qmc_probe: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!in || !out || n < 0 || n > (1ll << 28)) return set_error(YK_ERR_ARG, "yk_debug_qmc_probe: bad arguments");
   const bool ri = fn == YK_PROBE_RI_VDC || fn == YK_PROBE_RI_S || fn == YK_PROBE_RI_LP;
   if (ri && !in2) return set_error(YK_ERR_ARG, "yk_debug_qmc_probe: RI_* need the scramble words");
@@ -368,8 +368,7 @@ extern "C" int yk_debug_qmc_probe(yk_device* d, int32_t fn, const void* in, cons
 }
 
 extern "C" int yk_debug_small_scene(yk_device* d, int64_t* bytes) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_small_scene: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !bytes) return set_error(YK_ERR_ARG, "yk_debug_small_scene: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_small_scene: no scene uploaded");
   *bytes = (d->small && !d->big_leaves) ? (int64_t)d->small_bytes : 0;
@@ -377,8 +376,7 @@ extern "C" int yk_debug_small_scene(yk_device* d, int64_t* bytes) {
 }
 
 extern "C" int yk_debug_shading_kind(yk_device* d, int32_t* diff_only) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_shading_kind: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !diff_only) return set_error(YK_ERR_ARG, "yk_debug_shading_kind: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_shading_kind: no scene uploaded");
   *diff_only = d->shade.mat == kMatDiffuse ? 1 : 0;
@@ -386,8 +384,7 @@ extern "C" int yk_debug_shading_kind(yk_device* d, int32_t* diff_only) {
 }
 
 extern "C" int yk_debug_shadow_form(yk_device* d, const yk_render_params* p, int32_t* split) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_shadow_form: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !p || !split) return set_error(YK_ERR_ARG, "yk_debug_shadow_form: bad arguments");
   if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_debug_shadow_form: no scene uploaded");
   *split = shadow_split(d, p) ? 1 : 0;
@@ -395,16 +392,14 @@ extern "C" int yk_debug_shadow_form(yk_device* d, const yk_render_params* p, int
 }
 
 extern "C" int yk_debug_batch_plan(const yk_batch_plan_in* in, yk_batch_plan* out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_batch_plan: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!in || !out) return set_error(YK_ERR_ARG, "yk_debug_batch_plan: bad arguments");
   if (const char* why = plan_batches(*in, *out)) return set_error(YK_ERR_UNSUPPORTED, why);
   return YK_OK;
 }
 
 extern "C" int yk_debug_last_plan(yk_device* d, yk_last_plan* out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_last_plan: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !out) return set_error(YK_ERR_ARG, "yk_debug_last_plan: bad arguments");
   if (!d->last_plan_valid) return set_error(YK_ERR_STATE, "yk_debug_last_plan: no render yet");
   *out = yk_last_plan{};
@@ -505,16 +500,14 @@ static int debug_splat(yk_device* d, const yk_render_params* p, int32_t shard, i
 extern "C" int yk_debug_film_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards, int32_t spp,
                                    int32_t tiles_per_batch, const uint8_t* flags, const float* colours,
                                    const float* offsets, int64_t n, float* film) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_film_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   return debug_splat(d, p, shard, nshards, spp, tiles_per_batch, flags, colours, offsets, n, film, false);
 }
 
 extern "C" int yk_debug_depth_splat(yk_device* d, const yk_render_params* p, int32_t shard, int32_t nshards,
                                     int32_t spp, int32_t tiles_per_batch, const uint8_t* flags, const float* depths,
                                     const float* offsets, int64_t n, float* film) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_depth_splat: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   return debug_splat(d, p, shard, nshards, spp, tiles_per_batch, flags, depths, offsets, n, film, true);
 }
 
@@ -523,8 +516,7 @@ extern "C" int yk_debug_depth_splat(yk_device* d, const yk_render_params* p, int
 // true), reported as all ones.
 extern "C" int yk_debug_aa_flags(yk_device* d, const float* film, int32_t w, int32_t h, float threshold,
                                  uint8_t* flags_out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_aa_flags: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !film || !flags_out || w <= 0 || h <= 0 || (long long)w * h > (1ll << 24))
     return set_error(YK_ERR_ARG, "yk_debug_aa_flags: bad arguments");
   YK_GUARD_BEGIN
@@ -642,8 +634,7 @@ struct HostNearest {
 
 extern "C" int yk_debug_photon_load(yk_device* d, int32_t which, const float* photons, int32_t n, int32_t depth_limit,
                                     yk_photon_map_info* info) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_load: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !photon_slot_ok(which) || n < 0 || n > (1 << 24) || (n > 0 && !photons))
     return set_error(YK_ERR_ARG, "yk_debug_photon_load: bad arguments");
   YK_GUARD_BEGIN
@@ -685,8 +676,7 @@ extern "C" int yk_debug_photon_load(yk_device* d, int32_t which, const float* ph
 
 extern "C" int yk_debug_photon_gather(yk_device* d, int32_t which, const float* pos, const float* r2, int64_t nq,
                                       int32_t K, int32_t* count, int32_t* idx, float* d2, float* r2_out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_gather: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !photon_slot_ok(which) || nq < 0 || nq > kProbeMaxQueries ||
       (nq > 0 && (!pos || !r2 || !count || !idx || !d2 || !r2_out)))
     return set_error(YK_ERR_ARG, "yk_debug_photon_gather: bad arguments");
@@ -721,8 +711,7 @@ extern "C" int yk_debug_photon_gather(yk_device* d, int32_t which, const float* 
 
 extern "C" int yk_debug_photon_nearest(yk_device* d, int32_t which, const float* pos, const float* nrm,
                                        const float* r2, int64_t nq, int32_t* nearest) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_nearest: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || !photon_slot_ok(which) || nq < 0 || nq > kProbeMaxQueries || (nq > 0 && (!pos || !nrm || !r2 || !nearest)))
     return set_error(YK_ERR_ARG, "yk_debug_photon_nearest: bad arguments");
   if (nq == 0) return YK_OK;
@@ -749,8 +738,7 @@ extern "C" int yk_debug_photon_nearest(yk_device* d, int32_t which, const float*
 extern "C" int yk_debug_photon_lookup_queue(yk_device* d, const float* lq, int64_t nq, float rad2,
                                             int32_t force_scratch, float* lcol, int64_t ncol, int32_t* lds_out,
                                             int32_t* grid_out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_lookup_queue: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (!d || nq < 0 || nq > kProbeMaxQueue || ncol < 0 || ncol > 3 * kProbeMaxQueue || (nq > 0 && !lq) ||
       (ncol > 0 && !lcol))
     return set_error(YK_ERR_ARG, "yk_debug_photon_lookup_queue: bad arguments");
@@ -789,8 +777,7 @@ extern "C" int yk_debug_photon_lookup_queue(yk_device* d, const float* lq, int64
 
 extern "C" int yk_debug_photon_host_tree(const float* photons, int32_t n, uint32_t* nodes, int64_t cap_nodes,
                                          int32_t* nnodes, int32_t* depth) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_tree: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || cap_nodes < 0 || (cap_nodes > 0 && !nodes) || !nnodes || !depth)
     return set_error(YK_ERR_ARG, "yk_debug_photon_host_tree: bad arguments");
   YK_GUARD_BEGIN
@@ -808,8 +795,7 @@ extern "C" int yk_debug_photon_host_tree(const float* photons, int32_t n, uint32
 extern "C" int yk_debug_photon_host_gather(const float* photons, int32_t n, const float* pos, const float* r2,
                                            int64_t nq, int32_t K, int32_t* count, int32_t* idx, float* d2,
                                            float* r2_out) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_gather: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || nq < 0 || nq > kProbeMaxQueries ||
       (nq > 0 && (!pos || !r2 || !count || !idx || !d2 || !r2_out)))
     return set_error(YK_ERR_ARG, "yk_debug_photon_host_gather: bad arguments");
@@ -837,8 +823,7 @@ extern "C" int yk_debug_photon_host_gather(const float* photons, int32_t n, cons
 
 extern "C" int yk_debug_photon_host_nearest(const float* photons, int32_t n, const float* pos, const float* nrm,
                                             const float* r2, int64_t nq, int32_t* nearest) {
-  if (!debug_hooks_on())
-    return set_error(YK_ERR_UNSUPPORTED, "yk_debug_photon_host_nearest: test hook disabled (YK_DEBUG_HOOKS=1)");
+  YK_HOOK_ONLY;
   if (n < 0 || n > (1 << 24) || (n > 0 && !photons) || nq < 0 || nq > kProbeMaxQueries ||
       (nq > 0 && (!pos || !nrm || !r2 || !nearest)))
     return set_error(YK_ERR_ARG, "yk_debug_photon_host_nearest: bad arguments");

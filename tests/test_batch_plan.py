@@ -1,4 +1,4 @@
-"""The batch planner (plan_batches in core_amd/csrc/yk_device.hip, through
+"""The batch planner (plan_batches in core_amd/csrc/yk_pipe_host.inc, through
 yk_debug_batch_plan) on the host: no GPU.
 
 The planner sizes every per-batch buffer and with them every 32-bit index

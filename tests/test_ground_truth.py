@@ -315,7 +315,7 @@ def test_device_vs_float64(gpu_device, monkeypatch, name, small, lds):
     gpu_device.upload(s)
     assert (_small_bytes(gpu_device) > 0) == lds  # the kernel family under test
     if name == "hair":
-        # yk_device.hip crowded(): a tree is crowded when its mean references per
+        # yk_upload_host.inc crowded(): a tree is crowded when its mean references per
         # filled leaf exceed YK_CROWDED_LEAF (default 8). At 300 strands the
         # mean is 2.8: the default takes the ordinary ray hand-out, and
         # test_device_hair_crowded_leaf_path forces the other one.
