@@ -1195,13 +1195,20 @@ struct RaySrc {
   unsigned omask, kshift, kstride;
 };
 
-template <bool CLOSEST, int NSEG, bool TS = false, bool BIG = false, bool UNI = false, int W = 1, bool SPLIT = false,
-          bool GROUP = false, bool GLT = false>
+// trace_body's FLAGS: transparent shadows (filter colours, up to ts_depth
+// surfaces), a leaf of 2^17 references or more (coop_leaves BIG), a
+// universal-mode scene (t > tmin), split shadow slots (RaySrc), the camera
+// rays' group hand-out, glass transparency in the leaf body (mat_transparency<true>)
+constexpr unsigned kTrTS = 1, kTrBig = 2, kTrUni = 4, kTrSplit = 8, kTrGroup = 16, kTrGlt = 32;
+
+template <bool CLOSEST, int NSEG, int W = 1, unsigned FLAGS = 0>
 __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned* __restrict__ idx,
                                            RayCount rc, yk_hit* __restrict__ hits, uint8_t* __restrict__ occl,
                                            unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,
                                            uint2* __restrict__ ovf, int ovf_depth, int refill_min,
                                            float* __restrict__ tsf = nullptr, int ts_depth = 0) {
+  constexpr bool TS = (FLAGS & kTrTS) != 0, BIG = (FLAGS & kTrBig) != 0, UNI = (FLAGS & kTrUni) != 0,
+                 SPLIT = (FLAGS & kTrSplit) != 0, GROUP = (FLAGS & kTrGroup) != 0, GLT = (FLAGS & kTrGlt) != 0;
   static_assert(!GROUP || (CLOSEST && !TS && !UNI && !SPLIT), "the group hand-out serves the camera-ray closest-hit kernels");
   using KeyT = std::conditional_t<CLOSEST, unsigned long long, unsigned>;
   constexpr int R = W > 1 ? YK_SMALL_RING : (CLOSEST ? kStackLdsC : kStackLds);
@@ -1686,77 +1693,60 @@ __device__ __forceinline__ void trace_body(DScene S, RaySrc src, const unsigned*
 #define YK_SHADOW_WAVES 7
 #endif
 
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_closest(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-               yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-               unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, YK_SHADOW_SEGS>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);
-}
-// the same over a batch's split shadow slots (RaySrc)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_split(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                     yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                     unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, YK_SHADOW_SEGS, false, false, false, 1, true>(S, src, idx, n, hits, occl, work, ctr, ovf,
-                                                                   ovf_depth, refill_min);
-}
-// camera rays: the closest-hit kernel with the group hand-out (trace_body
-// GROUP); refill_min is unused
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_camera(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-               yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-               unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8, false, false, false, 1, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
-                                                           refill_min);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_camera_big(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                   yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8, false, true, false, 1, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
-                                                          refill_min);
-}
-// trees with a leaf of 2^17 references or more (coop_leaves BIG)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_closest_big(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                    yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                    unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_big(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                   yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);
-}
-// universal-mode scenes (kdTree_t<primitive_t>::IntersectS: t > tmin)
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_uni(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                   yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, false, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
-                                                        refill_min);
-}
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_big_uni(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                       yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                       unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, false, true, true>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);
-}
+// The trace kernels of one signature, written once: X(enumerator, kernel,
+// amdgpu_waves_per_eu, waves per workgroup, LDS ring depth per lane, body).
+// Expanded here into the kernels and in yk_device_host.inc into TraceVariant
+// and kTrace, so a kernel always meets its own workgroup size and ring; a new
+// trace kernel is one line. The order is the order of the kernels in the
+// code object. First the kernels of large trees (traversal data in HBM):
+// plain, over a batch's split shadow slots (kTrSplit), camera rays with the
+// group hand-out (kTrGroup; refill_min is unused), trees with a leaf of 2^17
+// references or more (kTrBig), universal-mode scenes
+// (kdTree_t<primitive_t>::IntersectS: t > tmin, kTrUni). Then the small
+// scenes: traversal data in LDS, YK_SMALL_W waves per workgroup, dynamic
+// LDS = small_scene_bytes.
+#define YK_TRACE_VARIANTS_LARGE(X)                                                                                    \
+  X(kClosest, k_trace_closest, YK_CLOSEST_WAVES, 1, kStackLdsC, trace_body<true, 8>)                                  \
+  X(kShadow, k_trace_shadow, YK_SHADOW_WAVES, 1, kStackLds, trace_body<false, YK_SHADOW_SEGS>)                        \
+  X(kShadowSplit, k_trace_shadow_split, YK_SHADOW_WAVES, 1, kStackLds, trace_body<false, YK_SHADOW_SEGS, 1, kTrSplit>) \
+  X(kCamera, k_trace_camera, YK_CLOSEST_WAVES, 1, kStackLdsC, trace_body<true, 8, 1, kTrGroup>)                       \
+  X(kCameraBig, k_trace_camera_big, YK_CLOSEST_WAVES, 1, kStackLdsC, trace_body<true, 8, 1, kTrBig | kTrGroup>)       \
+  X(kClosestBig, k_trace_closest_big, YK_CLOSEST_WAVES, 1, kStackLdsC, trace_body<true, 8, 1, kTrBig>)                \
+  X(kShadowBig, k_trace_shadow_big, YK_SHADOW_WAVES, 1, kStackLds, trace_body<false, 1, 1, kTrBig>)                   \
+  X(kShadowUni, k_trace_shadow_uni, YK_SHADOW_WAVES, 1, kStackLds, trace_body<false, 1, 1, kTrUni>)                   \
+  X(kShadowBigUni, k_trace_shadow_big_uni, YK_SHADOW_WAVES, 1, kStackLds, trace_body<false, 1, 1, kTrBig | kTrUni>)
+#define YK_TRACE_VARIANTS_SMALL(X)                                                                                    \
+  X(kClosestSmall, k_trace_closest_small, YK_CLOSEST_WAVES, YK_SMALL_W, YK_SMALL_RING,                                \
+    trace_body<true, 8, YK_SMALL_W>)                                                                                  \
+  X(kCameraSmall, k_trace_camera_small, YK_CLOSEST_WAVES, YK_SMALL_W, YK_SMALL_RING,                                  \
+    trace_body<true, 8, YK_SMALL_W, kTrGroup>)                                                                        \
+  X(kShadowSmall, k_trace_shadow_small, YK_SHADOW_WAVES, YK_SMALL_W, YK_SMALL_RING,                                   \
+    trace_body<false, YK_SHADOW_SEGS, YK_SMALL_W>)                                                                    \
+  X(kShadowSmallSplit, k_trace_shadow_small_split, YK_SHADOW_WAVES, YK_SMALL_W, YK_SMALL_RING,                        \
+    trace_body<false, YK_SHADOW_SEGS, YK_SMALL_W, kTrSplit>)                                                          \
+  X(kShadowUniSmall, k_trace_shadow_uni_small, YK_SHADOW_WAVES, YK_SMALL_W, YK_SMALL_RING,                            \
+    trace_body<false, 1, YK_SMALL_W, kTrUni>)
+#define YK_TRACE_VARIANTS(X) YK_TRACE_VARIANTS_LARGE(X) YK_TRACE_VARIANTS_SMALL(X)
+
+#define YK_TRACE_KERNEL(id, name, wpe, W, ring, ...)                                                                  \
+  __global__ void __launch_bounds__(64 * (W)) __attribute__((amdgpu_waves_per_eu(wpe)))                               \
+  name(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n, yk_hit* __restrict__ hits,                 \
+       uint8_t* __restrict__ occl, unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,       \
+       uint2* __restrict__ ovf, int ovf_depth, int refill_min) {                                                      \
+    __VA_ARGS__(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth, refill_min);                                   \
+  }
+
+YK_TRACE_VARIANTS_LARGE(YK_TRACE_KERNEL)
+// The two transparent-shadow kernels take two more arguments and stay out of
+// the list (enqueue_trace_ts, per_cu_ts); they keep their place between the
+// listed kernels.
 // transparent shadows (scene_t::isShadowed(state, ray, maxDepth, filt),
 // scene.cc:904-928 -> IntersectTS): occlusion + filter colour per ray
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5)))
 k_trace_shadow_ts(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
                   uint8_t* __restrict__ occl, float* __restrict__ tsf, int ts_depth, unsigned long long* __restrict__ work,
                   unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, true>(S, src, idx, n, nullptr, occl, work, ctr, ovf, ovf_depth, refill_min, tsf,
-                                    ts_depth);
+  trace_body<false, 1, 1, kTrTS>(S, src, idx, n, nullptr, occl, work, ctr, ovf, ovf_depth, refill_min, tsf, ts_depth);
 }
 // the same for scenes that hold a glass with fake shadows: glassMat_t::getTransparency in the leaf body
 // (mat_transparency<true>); no other scene launches it
@@ -1765,47 +1755,11 @@ k_trace_shadow_ts_glass(DScene S, RaySrc src, const unsigned* __restrict__ idx, 
                         uint8_t* __restrict__ occl, float* __restrict__ tsf, int ts_depth,
                         unsigned long long* __restrict__ work, unsigned long long* __restrict__ ctr,
                         uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, true, false, false, 1, false, false, true>(S, src, idx, n, nullptr, occl, work, ctr, ovf,
-                                                                  ovf_depth, refill_min, tsf, ts_depth);
+  trace_body<false, 1, 1, kTrTS | kTrGlt>(S, src, idx, n, nullptr, occl, work, ctr, ovf, ovf_depth, refill_min, tsf,
+                                          ts_depth);
 }
-// small scenes (traversal data in LDS, YK_SMALL_W waves per workgroup;
-// dynamic LDS = small_scene_bytes)
-__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_closest_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                      yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                      unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8, false, false, false, YK_SMALL_W>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
-                                                       refill_min);
-}
-__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_CLOSEST_WAVES)))
-k_trace_camera_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                     yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                     unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<true, 8, false, false, false, YK_SMALL_W, false, true>(S, src, idx, n, hits, occl, work, ctr, ovf,
-                                                                    ovf_depth, refill_min);
-}
-__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                     yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                     unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, YK_SHADOW_SEGS, false, false, false, YK_SMALL_W>(S, src, idx, n, hits, occl, work, ctr, ovf,
-                                                                     ovf_depth, refill_min);
-}
-__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_small_split(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                           yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                           unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth,
-                           int refill_min) {
-  trace_body<false, YK_SHADOW_SEGS, false, false, false, YK_SMALL_W, true>(S, src, idx, n, hits, occl, work, ctr,
-                                                                           ovf, ovf_depth, refill_min);
-}
-__global__ void __launch_bounds__(64 * YK_SMALL_W) __attribute__((amdgpu_waves_per_eu(YK_SHADOW_WAVES)))
-k_trace_shadow_uni_small(DScene S, RaySrc src, const unsigned* __restrict__ idx, RayCount n,
-                         yk_hit* __restrict__ hits, uint8_t* __restrict__ occl, unsigned long long* __restrict__ work,
-                         unsigned long long* __restrict__ ctr, uint2* __restrict__ ovf, int ovf_depth, int refill_min) {
-  trace_body<false, 1, false, false, true, YK_SMALL_W>(S, src, idx, n, hits, occl, work, ctr, ovf, ovf_depth,
-                                                       refill_min);
-}
+YK_TRACE_VARIANTS_SMALL(YK_TRACE_KERNEL)
+#undef YK_TRACE_KERNEL
 
 // ============================================================ shading
 
@@ -4498,644 +4452,8 @@ __global__ void __launch_bounds__(256) k_finish(Batch B, RenderConst R, long lon
   B.samples[c] = make_float4(col.r, col.g, col.b, B.alpha[c]);
 }
 
-// ------------------------------------------------------------ specular recursion
-//
-// mcIntegrator_t::recursiveRaytrace (mcintegrator.cc:421-627) calls the
-// integrator again for the mirror and refraction rays of a specular hit, up
-// to raydepth levels. Here every such call is an entry ("node") of a later
-// generation: generation g holds the rays of recursion level g, shaded by the
-// same kernels as camera rays. Each node keeps its own terms (emission,
-// direct light, path estimate) and its children; k_fold then sums every
-// camera sample's tree in the reference's order. state.includeLights is
-// shared by the recursive calls, and lightMat_t::emit reads it, so a node's
-// emission is only added at the fold, where the value left by the previous
-// sibling's subtree is known (pathtracer.cc:149-152,220,264; directlight.cc
-// restores it on return).
-
-enum : int { NF_HIT = 1, NF_LIGHT = 2, NF_LOOP = 4, NF_LOOPT = 8, NF_SPEC = 16 };
-
-struct NodeStore {
-  float* E;      // 3 per node: emission at the node's hit (includeLights = true)
-  float* D;      // 3 per node: direct light (or background on a miss)
-  float* P;      // 3 per node: pathCol / nSamples (path tracer)
-  int* flags;    // NF_*
-  int* child;    // 2 per node: reflect, refract (-1 none)
-  float* rcol;   // 6 per node: getSpecular colours of the two children
-  float* alpha;  // camera nodes
-  yk_ray* ray;   // rays of nodes of generation >= 1 (by node id)
-  unsigned* soffs;
-  unsigned* psample;
-  unsigned long long* count;  // allocated node ids
-  long long cap;
-  int* overflow;
-  float* malpha;  // photon mapping: material_t::getAlpha at the node's hit (1 unless transparent)
-};
-
-// Terms of the n entries of one chunk (node ids base..base+n-1).
-__global__ void __launch_bounds__(256) k_finish_spec(Batch B, RenderConst R, NodeStore NS, long long base,
-                                                     long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long long node = base + i;
-  const int ph = B.prim_hit[i];
-  const bool loop = R.integrator == YK_INTEGRATOR_PATH && (ph & PH_DIFFUSE);
-  c3 P = C3(0.f, 0.f, 0.f);
-  if (loop) {
-    const float ns = (float)R.nsub;
-    P = C3(B.pathcol[3 * i] / ns, B.pathcol[3 * i + 1] / ns, B.pathcol[3 * i + 2] / ns);
-  }
-  int f = 0;
-  if (ph & PH_HIT) f |= NF_HIT;
-  if (ph & PH_LIGHT) f |= NF_LIGHT;
-  if (loop) f |= NF_LOOP | (B.incl[i] ? NF_LOOPT : 0);
-  NS.flags[node] = f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    NS.E[3 * node + k] = (ph & PH_HIT) ? B.emit0[3 * i + k] : 0.f;
-    NS.D[3 * node + k] = B.col[3 * i + k];
-  }
-  NS.P[3 * node] = P.r;
-  NS.P[3 * node + 1] = P.g;
-  NS.P[3 * node + 2] = P.b;
-  NS.child[2 * node] = -1;
-  NS.child[2 * node + 1] = -1;
-  NS.malpha[node] = 1.f;
-  if (R.level == 0) NS.alpha[node] = B.alpha[i];
-}
-
-// recursiveRaytrace's specular block for the hits of one chunk: allocate the
-// reflect / refract children (rays from sp.P, tmin MIN_RAYDIST, unbounded).
-// GL: as in the shading kernels (a coated glossy material's getSpecular).
-template <int GL = kGLNone>
-__global__ void __launch_bounds__(256) k_spawn(DScene S, Batch B, RenderConst R, NodeStore NS, long long base,
-                                               long long n) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || !(B.prim_hit[i] & PH_HIT)) return;
-  const int lv = R.level + 1;  // state.raylevel++
-  if (lv > R.rdepth || lv >= 20) return;
-  const yk_hit h = B.p_hits[i];
-  const yk_ray r = B.p_rays[i];
-  const v3 from = V3(r.from[0], r.from[1], r.from[2]), dir = V3(r.dir[0], r.dir[1], r.dir[2]);
-  const SurfPt sp = make_surface(S, from, dir, h);
-  const DMat& M = c_mats[sp.mat];
-  if (!(M.flags & (BSDF_SPECULAR | BSDF_FILTER))) return;
-  const long long node = base + i;
-  NS.flags[node] |= NF_SPEC;
-  bool glass = false;
-  if constexpr (GL >= kGLGlass) glass = M.type == YK_MAT_GLASS;
-  if (glass) {  // glassMat_t::getAlpha, whether or not it fakes shadows
-    if (R.integrator == YK_INTEGRATOR_PHOTON) NS.malpha[node] = glass_alpha(M, sp, vneg(dir));
-  } else if (R.integrator == YK_INTEGRATOR_PHOTON && (M.flags & BSDF_FILTER)) {
-    // shinyDiffuseMat_t::getAlpha (shinydiffuse.cc:457-469) of a transparent material
-    const v3 wo = vneg(dir);
-    const float Kr = mat_fresnel(M, wo, face_forward(sp.Ng, sp.N, wo));
-    const float refl = (1.f - M.comp[0] * Kr) * M.comp[1];
-    NS.malpha[node] = 1.f - refl;
-  }
-  bool refl, refr;
-  v3 d[2];
-  c3 col[2];
-  mat_specular<GL>(M, sp, vneg(dir), refl, refr, d, col, lv);
-  const bool want[2] = {refl, refr};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    if (!want[k]) continue;
-    const unsigned long long id = atomicAdd(NS.count, 1ull);
-    if ((long long)id >= NS.cap) {
-      *NS.overflow = 1;
-      continue;
-    }
-    NS.child[2 * node + k] = (int)id;
-    NS.rcol[6 * node + 3 * k] = col[k].r;
-    NS.rcol[6 * node + 3 * k + 1] = col[k].g;
-    NS.rcol[6 * node + 3 * k + 2] = col[k].b;
-    put_ray(NS.ray[id], sp.P, d[k], YK_MIN_RAYDIST, -1.0f);
-    NS.soffs[id] = B.soffs[i];
-    NS.psample[id] = B.psample[i];
-  }
-}
-
-// Sums each camera sample's node tree depth first, in the reference's order:
-// col = (emit + direct) + path; col += child_r * rcol0; col += child_t * rcol1.
-__global__ void __launch_bounds__(256) k_fold(Batch B, RenderConst R, NodeStore NS, long long nc) {
-  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  constexpr int kMaxLevel = 22;
-  int nodes[kMaxLevel], stage[kMaxLevel];
-  c3 acc[kMaxLevel];
-  float alp[kMaxLevel];  // photon mapping: integrate()'s alpha, set by the refract child
-  const bool pt = R.integrator == YK_INTEGRATOR_PATH, pm = R.integrator == YK_INTEGRATOR_PHOTON;
-  const float a_init = R.transp_bg ? 0.f : 1.f;
-  float result_alpha = 0.f;
-  bool e = true;  // state.includeLights
-  int dd = 0;
-  nodes[0] = (int)c;
-  stage[0] = 0;
-  c3 result = C3(0.f, 0.f, 0.f);
-  for (;;) {
-    const int n = nodes[dd];
-    const int F = NS.flags[n];
-    if (stage[dd] == 0) {
-      c3 col = C3(NS.D[3 * n], NS.D[3 * n + 1], NS.D[3 * n + 2]);
-      if (F & NF_HIT) {
-        if (dd == 0) e = true;  // raylevel 0: includeLights = true
-        const bool incl = pt ? e : true;
-        const c3 E = ((F & NF_LIGHT) && !incl) ? C3(0.f, 0.f, 0.f)
-                                               : C3(NS.E[3 * n], NS.E[3 * n + 1], NS.E[3 * n + 2]);
-        col = cadd(E, col);
-        col = cadd(col, C3(NS.P[3 * n], NS.P[3 * n + 1], NS.P[3 * n + 2]));
-        if (pt && (F & NF_LOOP)) e = (F & NF_LOOPT) != 0;
-        if (F & NF_SPEC) e = true;
-      }
-      acc[dd] = col;
-      alp[dd] = a_init;
-      stage[dd] = 1;
-      const int ch = (F & NF_HIT) ? NS.child[2 * n] : -1;
-      if (ch >= 0 && dd + 1 < kMaxLevel) {
-        ++dd;
-        nodes[dd] = ch;
-        stage[dd] = 0;
-        continue;
-      }
-    }
-    if (stage[dd] == 1) {
-      stage[dd] = 2;
-      const int ch = (F & NF_HIT) ? NS.child[2 * n + 1] : -1;
-      if (ch >= 0 && dd + 1 < kMaxLevel) {
-        ++dd;
-        nodes[dd] = ch;
-        stage[dd] = 0;
-        continue;
-      }
-    }
-    const c3 v = acc[dd];
-    // photonintegr.cc:862-866: alpha = m_alpha + (1 - m_alpha) * alpha on a hit
-    const float m = NS.malpha[n];
-    const float va = (F & NF_HIT) ? m + (1.f - m) * alp[dd] : a_init;
-    if (dd == 0) {
-      result = v;
-      result_alpha = va;
-      break;
-    }
-    --dd;
-    const int pn = nodes[dd];
-    const int k = stage[dd] - 1;
-    if (k == 1) alp[dd] = va;  // recursiveRaytrace: alpha = integ.A of the refracted ray
-    const float* rc = NS.rcol + 6 * pn + 3 * k;
-    acc[dd] = cadd(acc[dd], C3(v.r * rc[0], v.g * rc[1], v.b * rc[2]));
-  }
-  B.samples[c] = make_float4(result.r, result.g, result.b, pm ? result_alpha : NS.alpha[c]);
-}
-
-// ------------------------------------------------------------ film
-
-struct FilmConst {
-  int cx0, cy0, cx1, cy1, w, h;  // film area (imagefilm.cc:119-127)
-  int tile, ntx;                 // tile size, tiles per row (imagesplitter.cc:29-53)
-  float filterw;
-  double tableScale;
-  int olo_x, ohi_x, olo_y, ohi_y;  // target-source offset window
-  int shard, nshards;
-  int tb0, tb1;                  // batch = owned tile ranks [tb0, tb1)
-  const int* rank_of;            // custom tile order: rank of each tile in the shard's list (-1: not owned); null: row-major
-  int spp;
-  float d1;
-  const int* pmap;  // adaptive pass: batch-local first sample of each film pixel, -1 = not resampled
-  float table[256];
-};
-
-__device__ __forceinline__ int round2int(double v) { return (int)(v + (0.5 - 1.4e-11)); }
-constexpr int kGatherGroup = 8;  // samples loaded per group (16 measured equal)
-__device__ __forceinline__ int floor2int(double v) { return (int)floor(v); }
-
-// Footprint extent of every source pixel of a batch: over its samples, the
-// smallest dx0 / dy0 and the largest dx1 / dy1 of addSample's target window
-// (the same Round2Int expressions as the gather). A target offset outside
-// them can take no sample of the pixel, so the gather skips the pixel's
-// sample loop: with a box filter a pixel's samples reach its 8 neighbours
-// almost never, and those loops were ~8/9 of the gather's work. One wave per
-// pixel slot (slot i = samples [i*spp, (i+1)*spp) of the batch).
-__global__ void __launch_bounds__(256) k_pixel_extent(FilmConst F, const float2* __restrict__ sxy,
-                                                      char4* __restrict__ ext, long long npix) {
-  const long long slot = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  if (slot >= npix) return;
-  int x0 = 127, x1 = -128, y0 = 127, y1 = -128;
-  for (int s = lane; s < F.spp; s += 64) {
-    const float2 d = sxy[slot * F.spp + s];
-    const double dx = d.x, dy = d.y;
-    x0 = min(x0, round2int(dx - F.filterw));
-    x1 = max(x1, round2int(dx + F.filterw - 1.0));
-    y0 = min(y0, round2int(dy - F.filterw));
-    y1 = max(y1, round2int(dy + F.filterw - 1.0));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    x0 = min(x0, __shfl_xor(x0, off));
-    x1 = max(x1, __shfl_xor(x1, off));
-    y0 = min(y0, __shfl_xor(y0, off));
-    y1 = max(y1, __shfl_xor(y1, off));
-  }
-  if (lane == 0) ext[slot] = make_char4((signed char)x0, (signed char)x1, (signed char)y0, (signed char)y1);
-}
-
-// What a gather adds up, as a policy of the shared walk (film_gather_walk):
-// the sample type, the pixel's sums (loaded from and stored to the film) and
-// the per-contribution arithmetic. GatherColour<false, false> is the film of
-// every render without film options, with the arithmetic the gather has
-// always had; the other instantiations are chosen on the host
-// (launch_film_gather) and cost those renders nothing.
-//
-// CLAMP: colorA_t::clampRGB01 once per sample, on load (imagefilm.cc:457,
-// color.h:119-124; a NaN passes both comparisons and stays). PREMULT:
-// addSample premultiplies its local copy inside the pixel loop (imagefilm.cc:
-// 502), so the m-th pixel of the sample's window, row-major after the clamp
-// to the film area, takes the colour after m sequential RGB *= A.
-template <bool CLAMP, bool PREMULT>
-struct GatherColour {
-  using Sample = float4;
-  static constexpr bool kPremult = PREMULT;
-  static constexpr int kStride = 5;
-  float aR, aG, aB, aA, aW;
-  __device__ __forceinline__ void load(const float* px) {
-    aR = px[0];
-    aG = px[1];
-    aB = px[2];
-    aA = px[3];
-    aW = px[4];
-  }
-  __device__ __forceinline__ void store(float* px) const {
-    px[0] = aR;
-    px[1] = aG;
-    px[2] = aB;
-    px[3] = aA;
-    px[4] = aW;
-  }
-  static __device__ __forceinline__ Sample none() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-  static __device__ __forceinline__ Sample fetch(const Sample* __restrict__ s, long long i) {
-    float4 c = s[i];
-    if constexpr (CLAMP) {
-      c.x = c.x < 0.f ? 0.f : (c.x > 1.f ? 1.f : c.x);
-      c.y = c.y < 0.f ? 0.f : (c.y > 1.f ? 1.f : c.y);
-      c.z = c.z < 0.f ? 0.f : (c.z > 1.f ? 1.f : c.z);
-    }
-    return c;
-  }
-  // -> whether the contribution counts
-  __device__ __forceinline__ bool add(float wt, Sample c, int m) {
-    if constexpr (PREMULT) {
-      for (int i = 0; i < m; ++i) {
-        c.x = c.x * c.w;
-        c.y = c.y * c.w;
-        c.z = c.z * c.w;
-      }
-    }
-    aR = aR + wt * c.x;
-    aG = aG + wt * c.y;
-    aB = aB + wt * c.z;
-    aA = aA + wt * c.w;
-    aW = aW + wt;
-    return true;
-  }
-};
-
-// imageFilm_t::addDepthSample (imagefilm.cc:513-564): one colour channel's
-// arithmetic plus the weight, on a film of {val, weight}. A NaN is a sample
-// without a depth value (k_depth_samples): it adds nothing, weight included.
-struct GatherDepth {
-  using Sample = float;
-  static constexpr bool kPremult = false;
-  static constexpr int kStride = 2;
-  float aV, aW;
-  __device__ __forceinline__ void load(const float* px) {
-    aV = px[0];
-    aW = px[1];
-  }
-  __device__ __forceinline__ void store(float* px) const {
-    px[0] = aV;
-    px[1] = aW;
-  }
-  static __device__ __forceinline__ Sample none() { return 0.f; }
-  static __device__ __forceinline__ Sample fetch(const Sample* __restrict__ s, long long i) { return s[i]; }
-  __device__ __forceinline__ bool add(float wt, Sample v, int) {
-    if (v != v) return false;
-    aV = aV + wt * v;
-    aW = aW + wt;
-    return true;
-  }
-};
-
-// imageFilm_t::addSample as a gather (imagefilm.cc:453-511): each thread owns
-// one target pixel and adds every covering sample of the batch in the
-// reference's single-thread order -- tiles in the order the film hands them
-// out (row-major, or the tile_order list), then rows, columns and samples --
-// so the float sums match the sequential CPU splat bit for bit.
-// Candidate sources are walked in that order directly: the tiles the filter
-// window touches in row-major tile order, inside each its window rows and
-// columns. The walk is shared by the colour film and the depth film (Acc).
-template <class Acc>
-__device__ __forceinline__ void film_gather_walk(const FilmConst& F, const typename Acc::Sample* __restrict__ samples,
-                                                 const float2* __restrict__ sxy, const int* __restrict__ tile_base,
-                                                 const char4* __restrict__ ext, float* __restrict__ film, int rx0,
-                                                 int ry0, int rw, int rh) {
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= rw * rh) return;
-  const int tx = rx0 + tid % rw, ty = ry0 + tid / rw;
-  if (tx < F.cx0 || tx >= F.cx1 || ty < F.cy0 || ty >= F.cy1) return;
-  // sources s with target - s in [olo, ohi]
-  const int sx0 = max(F.cx0, tx - F.ohi_x), sx1 = min(F.cx1 - 1, tx - F.olo_x);
-  const int sy0 = max(F.cy0, ty - F.ohi_y), sy1 = min(F.cy1 - 1, ty - F.olo_y);
-  if (sx0 > sx1 || sy0 > sy1) return;
-  const int tc0 = (sx0 - F.cx0) / F.tile, tc1 = (sx1 - F.cx0) / F.tile;
-  const int tr0 = (sy0 - F.cy0) / F.tile, tr1 = (sy1 - F.cy0) / F.tile;
-  float* px = film + Acc::kStride * ((size_t)(ty - F.cy0) * F.w + (tx - F.cx0));
-  Acc a;
-  a.load(px);
-  bool any = false;
-  // one tile of the batch: its source pixels in the window, rows, columns, samples
-  auto tile = [&](int tr, int tc, int rank) {
-      const int X = F.cx0 + tc * F.tile, Y = F.cy0 + tr * F.tile;
-      const int W = min(F.tile, F.cx1 - X);
-      const int ya = max(sy0, Y), yb = min(sy1, Y + F.tile - 1);
-      const int xa = max(sx0, X), xb = min(sx1, X + F.tile - 1);
-      const long long tb = tile_base[rank - F.tb0];
-      for (int sy = ya; sy <= yb; ++sy)
-        for (int sx = xa; sx <= xb; ++sx) {
-          long long cbase;
-          if (F.pmap) {
-            cbase = F.pmap[(size_t)(sy - F.cy0) * F.w + (sx - F.cx0)];
-            if (cbase < 0) continue;
-          } else {
-            cbase = tb + (long long)((sy - Y) * W + (sx - X)) * F.spp;
-          }
-          const int ox = tx - sx, oy = ty - sy;
-          {  // no sample of this source pixel reaches the target (k_pixel_extent)
-            const char4 e = ext[cbase / F.spp];
-            if (ox < e.x || ox > e.y || oy < e.z || oy > e.w) continue;
-          }
-          // samples in groups of kGatherGroup: the group's positions, then the
-          // colours of the accepted ones, are loaded together (independent
-          // loads in flight instead of one dependent round trip per sample);
-          // the sums still run sample by sample in order
-          for (int s0 = 0; s0 < F.spp; s0 += kGatherGroup) {
-            float2 dd[kGatherGroup];
-#pragma unroll
-            for (int k = 0; k < kGatherGroup; ++k)
-              dd[k] = (s0 + k < F.spp) ? sxy[cbase + s0 + k] : make_float2(-8.f, -8.f);
-            float wt[kGatherGroup];
-            bool acc[kGatherGroup];
-            int mm[Acc::kPremult ? kGatherGroup : 1];
-#pragma unroll
-            for (int k = 0; k < kGatherGroup; ++k) {
-              const double dx = dd[k].x, dy = dd[k].y;
-              const int dx0 = round2int(dx - F.filterw), dx1 = round2int(dx + F.filterw - 1.0);
-              const int dy0 = round2int(dy - F.filterw), dy1 = round2int(dy + F.filterw - 1.0);
-              // film-edge clamps (cx0 - x etc.) hold by construction: tx, ty lie inside the film
-              acc[k] = s0 + k < F.spp && !(ox < dx0 || ox > dx1 || oy < dy0 || oy > dy1);
-              wt[k] = 0.f;
-              if (acc[k]) {
-                const int xi = floor2int(fabs(((double)ox - (dx - 0.5)) * F.tableScale));
-                const int yi = floor2int(fabs(((double)oy - (dy - 0.5)) * F.tableScale));
-                wt[k] = F.table[yi * 16 + xi];
-                if constexpr (Acc::kPremult) {
-                  // the target's place in the sample's window after the clamp
-                  // to the film area, row-major from 1 (imagefilm.cc:463-466, 492-502)
-                  const int wx0 = max(F.cx0 - sx, dx0), wx1 = min(F.cx1 - sx - 1, dx1);
-                  const int wy0 = max(F.cy0 - sy, dy0);
-                  mm[k] = (oy - wy0) * (wx1 - wx0 + 1) + (ox - wx0) + 1;
-                }
-              }
-            }
-            typename Acc::Sample col[kGatherGroup];
-#pragma unroll
-            for (int k = 0; k < kGatherGroup; ++k)
-              col[k] = acc[k] ? Acc::fetch(samples, cbase + s0 + k) : Acc::none();
-#pragma unroll
-            for (int k = 0; k < kGatherGroup; ++k) {
-              if (!acc[k]) continue;
-              if (a.add(wt[k], col[k], Acc::kPremult ? mm[k] : 0)) any = true;
-            }
-          }
-        }
-  };
-  if (F.rank_of) {
-    // custom order (tiles_order "random"): the window's tiles of the batch by
-    // rank, the smallest rank above the previous one each time
-    int last = -1;
-    for (;;) {
-      int best = INT_MAX, btr = 0, btc = 0;
-      for (int r = tr0; r <= tr1; ++r)
-        for (int q = tc0; q <= tc1; ++q) {
-          const int k = F.rank_of[r * F.ntx + q];
-          if (k > last && k >= F.tb0 && k < F.tb1 && k < best) {
-            best = k;
-            btr = r;
-            btc = q;
-          }
-        }
-      if (best == INT_MAX) break;
-      last = best;
-      tile(btr, btc, best);
-    }
-  } else {
-    for (int tr = tr0; tr <= tr1; ++tr)  // row-major tiles
-      for (int tc = tc0; tc <= tc1; ++tc) {
-        const int ti = tr * F.ntx + tc;
-        if (ti % F.nshards != F.shard) continue;
-        const int rank = ti / F.nshards;
-        if (rank < F.tb0 || rank >= F.tb1) continue;
-        tile(tr, tc, rank);
-      }
-  }
-  if (!any) return;
-  a.store(px);
-}
-
-template <bool CLAMP, bool PREMULT>
-__global__ void __launch_bounds__(256) k_film_gather(FilmConst F, const float4* __restrict__ samples,
-                                                     const float2* __restrict__ sxy, const int* __restrict__ tile_base,
-                                                     const char4* __restrict__ ext, float* __restrict__ film,
-                                                     int rx0, int ry0, int rw, int rh) {
-  film_gather_walk<GatherColour<CLAMP, PREMULT>>(F, samples, sxy, tile_base, ext, film, rx0, ry0, rw, rh);
-}
-
-// The depth film's gather: the same walk over the batch's depth samples.
-__global__ void __launch_bounds__(256) k_depth_gather(FilmConst F, const float* __restrict__ depths,
-                                                      const float2* __restrict__ sxy, const int* __restrict__ tile_base,
-                                                      const char4* __restrict__ ext, float* __restrict__ film,
-                                                      int rx0, int ry0, int rw, int rh) {
-  film_gather_walk<GatherDepth>(F, depths, sxy, tile_base, ext, film, rx0, ry0, rw, rh);
-}
-
-// The depth sample of every camera sample of a batch (renderTile,
-// integrator.cc:313-334), after the batch's primary closest-hit launch:
-// c_ray.tmax is the camera hit's t (scene_t::intersect stores it, scene.cc:
-// 877), on a miss what shootRay left, the far plane's distance. Raw: tmax,
-// 99999997952.f where it is <= 0. Normalised: 1 - (tmax - minDepth) * maxDepth
-// where tmax > 0, else 0 (source order; contraction is off). A sample
-// without a ray (wt = 0, an angular camera's; cam_shoot gives it direction 0)
-// reaches `continue` before this point: NaN, which the gather skips.
-struct DepthConst {
-  int normalize;
-  float dmin, dinv;
-};
-__global__ void __launch_bounds__(256) k_depth_samples(const yk_ray* __restrict__ rays,
-                                                       const yk_hit* __restrict__ hits, float* __restrict__ out,
-                                                       DepthConst D, long long nc) {
-  const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  const yk_ray r = rays[c];
-  const yk_hit h = hits[c];
-  float depth;
-  if (r.dir[0] == 0.f && r.dir[1] == 0.f && r.dir[2] == 0.f && r.tmin == 0.f && r.tmax == -1.0f) {
-    depth = __int_as_float(0x7fc00000);
-  } else {
-    const float tmax = h.prim >= 0 ? h.t : r.tmax;
-    if (D.normalize) {
-      depth = 0.f;
-      if (tmax > 0.f) depth = 1.f - (tmax - D.dmin) * D.dinv;
-    } else {
-      depth = tmax;
-      if (depth <= 0.f) depth = 99999997952.f;
-    }
-  }
-  out[c] = depth;
-}
-
-// precalcDepths' rays (integrator.cc:116-121): shootRay(i, j, 0.5, 0.5) for
-// i < resY, j < resX -- the row index goes in as px -- in that order.
-template <int KIND>
-__global__ void __launch_bounds__(256) k_depth_range_rays(int resx, int resy, yk_ray* __restrict__ rays) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (long long)resx * resy) return;
-  const int i = (int)(t / resx), j = (int)(t % resx);
-  yk_ray r;
-  cam_shoot<KIND>((float)i, (float)j, 0.5f, 0.5f, r);
-  rays[t] = r;
-}
-
-// precalcDepths' min / max (integrator.cc:122-124) over the traced rays:
-// tmax = the hit's t, else the ray's own. Both are order-independent:
-// maxDepth starts at 0 and minDepth takes only tmax >= 0, so every value
-// that can win is a non-negative float, and those order as their bits do.
-// mm[0]: max bits (from 0), mm[1]: min bits (from 1e38f's).
-__global__ void __launch_bounds__(256) k_depth_range_reduce(const yk_ray* __restrict__ rays,
-                                                            const yk_hit* __restrict__ hits, long long n,
-                                                            unsigned* __restrict__ mm) {
-  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned hi = 0u, lo = 0xFFFFFFFFu;
-  if (t < n) {
-    const yk_hit h = hits[t];
-    float tmax = h.prim >= 0 ? h.t : rays[t].tmax;
-    if (tmax == 0.f) tmax = 0.f;  // -0 compares >= 0: its place is +0's
-    if (tmax >= 0.f) hi = lo = (unsigned)__float_as_int(tmax);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    hi = max(hi, (unsigned)__shfl_xor((int)hi, off));
-    lo = min(lo, (unsigned)__shfl_xor((int)lo, off));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (hi != 0u) atomicMax(mm, hi);
-    if (lo != 0xFFFFFFFFu) atomicMin(mm + 1, lo);
-  }
-}
-
-// yk_render_multi's reduce: acc = ((f[0] + f[1]) + f[2]) + ... in shard
-// order, one pass over all shard films (each element summed in the order the
-// sequential reduce added them, so the result does not depend on how the
-// copies were scheduled). Four floats per thread where the range allows.
-constexpr int kMaxMultiDev = 16;
-struct FilmShards {
-  const float* f[kMaxMultiDev];
-  int n;
-};
-__global__ void __launch_bounds__(256) k_film_sum(float* __restrict__ acc, FilmShards S, long long n) {
-  const long long i4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  if (i4 + 4 <= n) {
-    float4 a = *reinterpret_cast<const float4*>(S.f[0] + i4);
-    for (int k = 1; k < S.n; ++k) {
-      const float4 b = *reinterpret_cast<const float4*>(S.f[k] + i4);
-      a = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-    *reinterpret_cast<float4*>(acc + i4) = a;
-    return;
-  }
-  for (long long i = i4; i < n; ++i) {
-    float a = S.f[0][i];
-    for (int k = 1; k < S.n; ++k) a = a + S.f[k][i];
-    acc[i] = a;
-  }
-}
-
-// imageFilm_t::nextPass (imagefilm.cc:213-271): flag the pixels whose
-// brightness differs from a neighbour's by >= threshold. Compiled form: the
-// centre as abscol2bri of col*(1/w); each neighbour folded as
-// |(c - (0.0722*B)*inv) - (0.7152*G + 0.2126*R)*inv|, |c| when its weight is 0.
-__global__ void k_aa_flags(const float* __restrict__ film, int w, int h, float thr, uint8_t* __restrict__ flags) {
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= (w - 1) * (h - 1)) return;
-  const int x = tid % (w - 1), y = tid / (w - 1);
-  const float* a = film + 5 * ((size_t)y * w + x);
-  float c = 0.f;
-  if (a[4] > 0.f) {
-    const float inv = 1.0f / a[4];
-    c = (0.2126f * fabsf(a[0] * inv) + 0.7152f * fabsf(a[1] * inv)) + 0.0722f * fabsf(a[2] * inv);
-  }
-  auto differs = [&](int nx, int ny) {
-    const float* b = film + 5 * ((size_t)ny * w + nx);
-    float d = c;
-    if (b[4] > 0.f) {
-      const float inv = 1.0f / b[4];
-      d = (c - (0.0722f * b[2]) * inv) - (0.2126f * b[0] + 0.7152f * b[1]) * inv;
-    }
-    return fabsf(d) >= thr;
-  };
-  bool need = false;
-  if (differs(x + 1, y)) { need = true; flags[(size_t)y * w + x + 1] = 1; }
-  if (differs(x, y + 1)) { need = true; flags[(size_t)(y + 1) * w + x] = 1; }
-  if (differs(x + 1, y + 1)) { need = true; flags[(size_t)(y + 1) * w + x + 1] = 1; }
-  if (x > 0 && differs(x - 1, y + 1)) { need = true; flags[(size_t)(y + 1) * w + x - 1] = 1; }
-  if (need) flags[(size_t)y * w + x] = 1;
-}
-
-// imageFilm_t::flush: pixel_t::normalized (colorA_t / f multiplies by 1.0/f,
-// color.h:329-333) + clampRGB0 (imagefilm.cc:400-424); premult: the clamped
-// pixel's alphaPremultiply (imagefilm.cc:423)
-__global__ void k_film_resolve(const float* __restrict__ film, float* __restrict__ rgba, long long npx, int premult) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npx) return;
-  const float* a = film + 5 * p;
-  float r = 0.f, g = 0.f, b = 0.f, al = 0.f;
-  if (a[4] > 0.f) {
-    const float f = (float)(1.0 / (double)a[4]);
-    r = a[0] * f;
-    g = a[1] * f;
-    b = a[2] * f;
-    al = a[3] * f;
-  }
-  r = r < 0.f ? 0.f : r;
-  g = g < 0.f ? 0.f : g;
-  b = b < 0.f ? 0.f : b;
-  if (premult) {
-    r = r * al;
-    g = g * al;
-    b = b * al;
-  }
-  rgba[4 * p] = r;
-  rgba[4 * p + 1] = g;
-  rgba[4 * p + 2] = b;
-  rgba[4 * p + 3] = al;
-}
-
-// pixelGray_t::normalized (image_buffers.h:50-54): a float division
-__global__ void k_depth_resolve(const float* __restrict__ depth, float* __restrict__ z, long long npx) {
-  const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= npx) return;
-  const float v = depth[2 * p], w = depth[2 * p + 1];
-  z[p] = w > 0.f ? v / w : 0.f;
-}
+#include "yk_spec.inc"  // specular recursion: the node store, k_finish_spec, k_spawn, k_fold
+#include "yk_film.inc"  // FilmConst, k_pixel_extent, the gathers, the depth channel, the resolves
 
 #include "yk_photon.inc"
 
@@ -5145,700 +4463,11 @@ __global__ void k_depth_resolve(const float* __restrict__ depth, float* __restri
 
 using namespace yk;
 
-#include "yk_pipe_host.inc"  // HIPCHK, DBuf, launch, Pipe, pipes_env, plan_batches
-
-// The trace kernels of one signature, as a table. k_trace_shadow_ts takes two
-// more arguments (filter colours, depth) and stays on its own
-// (enqueue_trace_ts, per_cu_ts).
-enum TraceVariant {
-  kClosest, kShadow, kShadowSplit,                                    // large trees
-  kClosestBig, kShadowBig,                                            // a leaf of 2^17 references or more
-  kShadowUni, kShadowBigUni,                                          // universal-mode scenes
-  kClosestSmall, kShadowSmall, kShadowSmallSplit, kShadowUniSmall,  // traversal data in LDS
-  kCamera, kCameraBig, kCameraSmall,                                  // camera rays: group hand-out
-  kTraceVariants
-};
-using TraceKernel = void (*)(DScene, RaySrc, const unsigned*, RayCount, yk_hit*, uint8_t*, unsigned long long*,
-                             unsigned long long*, uint2*, int, int);
-struct TraceInfo {
-  TraceKernel kernel;
-  int waves;     // per workgroup
-  bool dyn_lds;  // small_bytes of dynamic LDS (the scene copy)
-  int ring;      // LDS stack ring depth per lane; deeper entries go to the overflow area
-};
-constexpr TraceInfo kTrace[kTraceVariants] = {
-    {k_trace_closest, 1, false, kStackLdsC},
-    {k_trace_shadow, 1, false, kStackLds},
-    {k_trace_shadow_split, 1, false, kStackLds},
-    {k_trace_closest_big, 1, false, kStackLdsC},
-    {k_trace_shadow_big, 1, false, kStackLds},
-    {k_trace_shadow_uni, 1, false, kStackLds},
-    {k_trace_shadow_big_uni, 1, false, kStackLds},
-    {k_trace_closest_small, YK_SMALL_W, true, YK_SMALL_RING},
-    {k_trace_shadow_small, YK_SMALL_W, true, YK_SMALL_RING},
-    {k_trace_shadow_small_split, YK_SMALL_W, true, YK_SMALL_RING},
-    {k_trace_shadow_uni_small, YK_SMALL_W, true, YK_SMALL_RING},
-    {k_trace_camera, 1, false, kStackLdsC},
-    {k_trace_camera_big, 1, false, kStackLdsC},
-    {k_trace_camera_small, YK_SMALL_W, true, YK_SMALL_RING},
-};
-
-// The shading kernels of a scene, as a table. A scene's variant is its
-// material level (the kernels' DIFF and GL arguments, which exclude each
-// other: mat_sample) and its light level (XL), both fixed at upload.
-// kMatDiffuse: every material a light or a one-component DIFFUSE|REFLECT shinydiffuse (mat_sample<true>);
-// kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated);
-// kMatGlass: one is glass (kGLGlass, which holds the glossy and coated code too)
-enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kMatGlass, kShadeMats };
-constexpr int kXLLevels = kXLSun + 1;
-struct ShadeVariant {
-  int mat = kMatGeneral;  // ShadeMat
-  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light; kXLSun: a sun
-};
-struct ShadeKernels {
-  decltype(&k_shade_primary<false, kXLNone, false>) primary[2];  // [AO]
-  decltype(&k_shade_bounce<false, kXLNone>) bounce;
-  int bounce_block;
-  decltype(&k_path_start<false>) path_start;
-  decltype(&k_spawn<>) spawn;
-  decltype(&k_fg_start<false>) fg_start;
-  decltype(&k_fg_hit<false>) fg_hit;
-  decltype(&k_photon_emit<>) photon_emit;
-  decltype(&k_pm_post<>) pm_post;
-  decltype(&k_pm_finish<>) pm_finish;
-  decltype(&k_pt_caustic<>) pt_caustic;
-  decltype(&k_photon_hit<>) photon_hit;
-};
-// Which instantiation a variant runs: DIFF (diffuse-only materials) and XL
-// (the scene holds a spot or sphere light). With the spot and sphere code in
-// every instantiation k_shade_primary grew from 105 / 123 to 117 / 132 VGPRs
-// (the general one from 4 to 3 waves per SIMD) and k_shade_bounce, held at 96,
-// spilled 8 / 58 VGPRs instead of 0 / 23; scenes without such a light
-// therefore run kernels that leave that code out (kXLNone), as scenes
-// with plain diffuse materials leave out the component loop.
-// A mesh light (kXLMesh) adds its own instantiations on top of the spot and
-// sphere code: meshLight_t::intersect walks the light's kd-tree per BSDF-half
-// sample with a per-lane stack in scratch memory (MeshStack), which no other
-// scene pays for.
-// A glossy material (GL) adds general-material instantiations of its own in
-// the same way, one per XL x AO: glossy's lobe code reaches no other scene.
-// Only k_shade_primary and k_shade_bounce sample lights, so only they take XL;
-// the photon, k_pm_* and k_pt_caustic kernels take GL alone; k_spawn differs
-// only for the coat (mat_specular), so glossy scenes run the general one.
-// A sun light (kXLSun) is the top level: its cone sampling and cone test, on
-// top of everything below. It is also the one sampled light beyond the area
-// light that photon maps accept, so at this level alone k_fg_hit (whose
-// estimateOneDirectLight may pick the sun) and k_photon_emit (emitPhoton)
-// have instantiations of their own; at every other level they are the
-// kernels they were before the sun.
-template <int MAT, int XL>
-constexpr ShadeKernels shade_cell() {
-  constexpr bool DIFF = MAT == kMatDiffuse;
-  constexpr int GL = MAT == kMatGlass ? kGLGlass : MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
-  return {{k_shade_primary<DIFF, XL, false, GL>, k_shade_primary<DIFF, XL, true, GL>}, k_shade_bounce<DIFF, XL, GL>,
-          bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL >= kGLCoated ? GL : kGLNone)>,
-          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL, (XL == kXLSun ? kXLSun : kXLNone)>,
-          k_photon_emit<(XL == kXLSun ? kXLSun : kXLNone)>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>,
-          k_photon_hit<GL>};
-}
-constexpr ShadeKernels kShade[kShadeMats][kXLLevels] = {
-    {shade_cell<kMatDiffuse, kXLNone>(), shade_cell<kMatDiffuse, kXLSpotSphere>(), shade_cell<kMatDiffuse, kXLMesh>(),
-     shade_cell<kMatDiffuse, kXLSun>()},
-    {shade_cell<kMatGeneral, kXLNone>(), shade_cell<kMatGeneral, kXLSpotSphere>(), shade_cell<kMatGeneral, kXLMesh>(),
-     shade_cell<kMatGeneral, kXLSun>()},
-    {shade_cell<kMatGlossy, kXLNone>(), shade_cell<kMatGlossy, kXLSpotSphere>(), shade_cell<kMatGlossy, kXLMesh>(),
-     shade_cell<kMatGlossy, kXLSun>()},
-    {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>(),
-     shade_cell<kMatCoated, kXLSun>()},
-    {shade_cell<kMatGlass, kXLNone>(), shade_cell<kMatGlass, kXLSpotSphere>(), shade_cell<kMatGlass, kXLMesh>(),
-     shade_cell<kMatGlass, kXLSun>()},
-};
-// below the sun's level the table names no instantiation beyond those it named before: no glossy k_spawn, no
-// DIFF or XL where a kernel takes none; the sun's level adds k_fg_hit and k_photon_emit of its own
-static_assert(kShade[kMatGlossy][kXLNone].spawn == kShade[kMatGeneral][kXLNone].spawn &&
-              kShade[kMatCoated][kXLNone].spawn != kShade[kMatGeneral][kXLNone].spawn &&
-              kShade[kMatDiffuse][kXLNone].photon_hit == kShade[kMatGeneral][kXLNone].photon_hit &&
-              kShade[kMatDiffuse][kXLNone].pm_post == kShade[kMatGeneral][kXLNone].pm_post &&
-              kShade[kMatCoated][kXLMesh].fg_hit == kShade[kMatCoated][kXLNone].fg_hit &&
-              kShade[kMatDiffuse][kXLMesh].path_start == kShade[kMatDiffuse][kXLNone].path_start &&
-              kShade[kMatGeneral][kXLMesh].photon_emit == kShade[kMatDiffuse][kXLNone].photon_emit &&
-              kShade[kMatCoated][kXLSun].fg_hit != kShade[kMatCoated][kXLNone].fg_hit &&
-              kShade[kMatDiffuse][kXLSun].photon_emit != kShade[kMatDiffuse][kXLNone].photon_emit &&
-              kShade[kMatDiffuse][kXLSun].path_start == kShade[kMatDiffuse][kXLNone].path_start);
-// the glass row names kernels of its own wherever the coated row does, and the coated row names what it named before
-static_assert(kShade[kMatCoated][kXLNone].spawn == &k_spawn<kGLCoated> &&
-              kShade[kMatCoated][kXLNone].bounce == &k_shade_bounce<false, kXLNone, kGLCoated> &&
-              kShade[kMatCoated][kXLNone].photon_hit == &k_photon_hit<kGLCoated> &&
-              kShade[kMatGlass][kXLNone].spawn == &k_spawn<kGLGlass> &&
-              kShade[kMatGlass][kXLNone].bounce != kShade[kMatCoated][kXLNone].bounce &&
-              kShade[kMatGlass][kXLNone].photon_hit != kShade[kMatCoated][kXLNone].photon_hit &&
-              kShade[kMatGlass][kXLMesh].fg_hit == kShade[kMatGlass][kXLNone].fg_hit &&
-              kShade[kMatGlass][kXLMesh].photon_emit == kShade[kMatDiffuse][kXLNone].photon_emit);
-
-struct yk_device {
-  int ordinal = 0;
-  int cus = 0;
-  int per_cu[kTraceVariants] = {};  // resident workgroups per CU of each trace kernel (fill_trace_occupancy)
-  // small scenes: traversal data copied to LDS per workgroup (install_traversal)
-  bool small = false;
-  size_t small_bytes = 0;
-  hipStream_t stream = nullptr;  // = pipe[0].stream (ray queries, film resolve)
-  bool uploaded = false;
-  const yk_scene* uploaded_scene = nullptr;  // the scene the resident arrays came from
-  uint64_t uploaded_gen = 0;                 // its Scene::generation at upload
-  uint64_t const_token = 0;                  // unique per yk_device_upload (bind_constants)
-  size_t nleaf = 0;                          // leaf-list entries of the resident tree
-  // scene
-  DBuf<float> tris;  // triangle records (kTriWords floats per prim)
-  DBuf<float4> ng;
-  DBuf<float> vn;  // smooth-shading vertex normals (9 per prim), only when the scene has smooth meshes
-  DBuf<uint2> nodes;
-  DBuf<uint32_t> pk;   // node packets (k_pack_nodes), rebuilt whenever nodes change
-  DBuf<float> ltris;  // leaf-ordered record copies, rebuilt whenever the leaf lists change
-  DBuf<uint32_t> leaf;
-  DScene S{};
-  int ntris = 0, max_depth = 0, nlights = 0, sum_light_slots = 0;
-  bool spec = false;  // some material has SPECULAR|FILTER components: recursion pipeline
-  ShadeVariant shade;  // material and light level of the scene: its shading kernels (shade_kernels)
-  // mesh lights: one record per light in DScene::ml, its arrays packed in three buffers
-  DBuf<DMeshLight> ml_recs;
-  DBuf<float> ml_f;
-  DBuf<uint2> ml_nodes;
-  DBuf<uint32_t> ml_leaf;
-  yk_abort_fn abort_fn = nullptr;  // yk_device_set_abort: polled between batches
-  void* abort_user = nullptr;
-  bool big_leaves = false;  // the resident tree has a leaf of 2^17 references or more: *_big kernels
-  bool crowded_leaves = false;  // mean references per non-empty leaf above YK_CROWDED_LEAF: 64-ray hand-out chunks
-  int refill = 24;  // idle lanes before a traversal wave refills (set_handout)
-  int refill_shadow = 24;  // the same for the any-hit kernels
-  int per_cu_ts = 1;
-  int per_cu_ts_glass = 1;  // k_trace_shadow_ts_glass
-  bool ts_glass = false;    // the scene holds a glass with fake shadows: transparent shadows run k_trace_shadow_ts_glass
-  int per_cu_lookup[2] = {1, 1};  // k_pm_lookup<false / true> resident waves per CU
-  // node store of the specular recursion (k_finish_spec / k_spawn / k_fold)
-  DBuf<float> nE, nD, nP, nrcol, nalpha, nmalpha;
-  DBuf<int> nflags, nchild, noverflow;
-  DBuf<yk_ray> nray;
-  DBuf<unsigned> nsoffs, npsample;
-  DBuf<unsigned long long> ncount, spec_words;
-  bool has_bg = false;
-  float bg[3] = {0.f, 0.f, 0.f};
-  std::vector<DLight> lights_host;
-  // photon maps of yk_photon_build (photonIntegrator_t::preprocess)
-  bool pm_ready = false;
-  int pm_integrator = -1;  // integrator whose preprocess built the maps
-  yk_photon_params pm_params{};
-  DBuf<uint2> dm_nodes, rm_nodes, cm_nodes;
-  DBuf<float4> dm_pos, dm_dir, dm_col, rm_pos, rm_dir, rm_col, cm_pos, cm_dir, cm_col;
-  DBuf<uint4> rm_pk;  // radiance tree as 16-B nodes (k_pm_lookup): split | axis, right; leaf: position | photon
-  std::vector<float> dm_host, rm_host, cm_host;  // 9 floats per photon, photon-vector order
-  int dm_paths = 0, cm_paths = 0;
-  int rm_depth = 0;  // radiance kd-tree depth (k_fg_hit keeps its lookup stack in LDS up to kLdsPStack)
-  size_t rm_nnodes = 0;  // radiance kd-tree nodes
-  std::vector<unsigned> mat_flags;  // bsdfFlags per material
-  Pipe pipe[kPipes];
-  hipEvent_t gather_ev[kPipes] = {};
-  // device records of the uploaded scene, kept to re-bind the GPU's constant
-  // memory when another handle on the same GPU uploaded a different scene
-  std::vector<DMat> mats_host;
-  DCam cam_host{};
-  // what precalcDepths reads of the camera (yk_depth_range): its resolution,
-  // and the clip values when it was set from parameters
-  int cam_resx = 0, cam_resy = 0;
-  bool cam_has_clip = false;
-  float cam_near_clip = 0.f, cam_far_clip = 0.f;
-  // yk_render_multi state, kept across calls (no allocation once sized): this
-  // device's shard film; as the reducing device, the sum, one staging film per
-  // peer GPU and one copy stream + event per peer (each peer's copy drives its
-  // own xGMI link)
-  DBuf<float> mfilm, macc;
-  DBuf<float> mdepth, mdacc;  // z_channel: this device's shard depth film; the reducing device's sum
-  DBuf<float> mstage[kMaxMultiDev];
-  DBuf<float> mdstage[kMaxMultiDev];  // z_channel: a peer GPU's shard depth film
-  // the frame plan's tile lists (upload_frame_plan; grow-only, so repeated renders allocate nothing)
-  DBuf<int4> tiles_dev;
-  DBuf<int> base_dev, pix_dev, pmap_dev, rank_dev;
-  DBuf<uint8_t> flags_dev;
-  // per batch of a render: the camera samples that carry a ray (an angular
-  // camera with `circular`; unused otherwise)
-  DBuf<unsigned long long> cam_live;
-  // the last render's batch plan (yk_debug_last_plan)
-  yk_batch_plan last_plan{};
-  bool last_plan_valid = false;
-  int last_max_batches = 0;
-  hipStream_t mstream[kMaxMultiDev] = {};
-  hipEvent_t mevent[kMaxMultiDev] = {};
-  ~yk_device() {
-    for (auto& e : gather_ev)
-      if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < kMaxMultiDev; ++i) {
-      if (mevent[i]) (void)hipEventDestroy(mevent[i]);
-      if (mstream[i]) (void)hipStreamDestroy(mstream[i]);
-    }
-  }
-};
-
-namespace {
-inline const ShadeKernels& shade_kernels(const yk_device* d) { return kShade[d->shade.mat][d->shade.xl]; }
-
-// Constant memory (c_mats, c_lights, c_cam) is per GPU, not per handle: the
-// upload whose records a GPU's constants hold. Every yk_device_upload takes a
-// fresh process-wide token (the scene's generation alone is not enough: the
-// camera can change on a built scene, yk_scene_set_camera, and a re-upload
-// must then reach c_cam). A handle whose token differs re-binds them before
-// it launches (bind_constants). If the records the GPU holds are byte-equal
-// to the handle's (handles of one scene on one GPU, as yk_render_multi's
-// concurrent threads have them), the handle adopts them without a copy, so
-// no handle rewrites constant memory while another one's kernels read it
-// (ADVICE r05).
-std::mutex g_const_mu;
-uint64_t g_const_token[64] = {};
-struct ConstImage {
-  std::vector<unsigned char> mats, lights, cam;
-};
-ConstImage g_const_img[64];
-std::atomic<uint64_t> g_upload_token{1};
-
-template <class T>
-void bytes_of(std::vector<unsigned char>& v, const T* p, size_t n) {
-  v.assign(reinterpret_cast<const unsigned char*>(p), reinterpret_cast<const unsigned char*>(p) + n * sizeof(T));
-}
-
-void bind_constants(yk_device* d) {
-  std::lock_guard<std::mutex> lk(g_const_mu);
-  const int o = d->ordinal & 63;
-  if (g_const_token[o] == d->const_token) return;
-  ConstImage img;
-  bytes_of(img.mats, d->mats_host.data(), d->mats_host.size());
-  bytes_of(img.lights, d->lights_host.data(), d->lights_host.size());
-  bytes_of(img.cam, &d->cam_host, 1);
-  ConstImage& cur = g_const_img[o];
-  if (g_const_token[o] != 0 && img.mats == cur.mats && img.lights == cur.lights && img.cam == cur.cam) {
-    g_const_token[o] = d->const_token;  // same records already resident: adopt, no rewrite
-    return;
-  }
-  if (!d->mats_host.empty())
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_mats), d->mats_host.data(), d->mats_host.size() * sizeof(DMat)));
-  if (!d->lights_host.empty())
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_lights), d->lights_host.data(), d->lights_host.size() * sizeof(DLight)));
-  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_cam), &d->cam_host, sizeof(DCam)));
-  g_const_token[o] = d->const_token;
-  cur = std::move(img);
-}
-
-// two handles render one frame only if their constant records are the same
-// (same scene generation is checked separately; this catches a camera, light
-// or material changed between the two uploads)
-bool same_constants(const yk_device* a, const yk_device* b) {
-  return a->mats_host.size() == b->mats_host.size() && a->lights_host.size() == b->lights_host.size() &&
-         std::memcmp(&a->cam_host, &b->cam_host, sizeof(DCam)) == 0 &&
-         (a->mats_host.empty() ||
-          std::memcmp(a->mats_host.data(), b->mats_host.data(), a->mats_host.size() * sizeof(DMat)) == 0) &&
-         (a->lights_host.empty() ||
-          std::memcmp(a->lights_host.data(), b->lights_host.data(), a->lights_host.size() * sizeof(DLight)) == 0) &&
-         a->has_bg == b->has_bg && std::memcmp(a->bg, b->bg, sizeof a->bg) == 0;
-}
-}  // namespace
-
-namespace {
-
-// the traversal watchdog fired (corrupt tree or stack): YK_ERR_INTERNAL
-struct watchdog_error : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define YK_GUARD_BEGIN try {
-#define YK_GUARD_END                                                                              \
-  }                                                                                               \
-  catch (const watchdog_error& e) { return set_error(YK_ERR_INTERNAL, e.what()); }               \
-  catch (const std::bad_alloc&) { return set_error(YK_ERR_ALLOC, "out of host memory"); }        \
-  catch (const std::invalid_argument& e) { return set_error(YK_ERR_ARG, e.what()); }             \
-  catch (const std::runtime_error& e) { return set_error(YK_ERR_HIP, e.what()); }                \
-  catch (const std::exception& e) { return set_error(YK_ERR_INTERNAL, e.what()); }               \
-  catch (...) { return set_error(YK_ERR_INTERNAL, "unknown C++ exception"); }
-
-// Structural check of a kd-tree in the export encoding (2 words per node:
-// split bits / single prim / leaf-list offset; axis | right child or count
-// << 2), before it becomes resident: every interior node i has its left child
-// at i + 1 and its right child r with i + 1 < r < nn, every node but the root
-// has exactly one parent, and every leaf references prims (single) or
-// leaf-list entries within range. Such a structure is a tree, so a traversal
-// visits each node at most once and its stack never holds more than the
-// depth. Returns the depth (root = 0), or -1 with *err set.
-int tree_depth(const uint32_t* w, size_t nn, size_t nleaf, size_t nprims, std::string* err) {
-  if (nn == 0) {
-    *err = "empty kd-tree";
-    return -1;
-  }
-  std::vector<uint8_t> parents(nn, 0), depth(nn, 0);
-  int maxd = 0;
-  for (size_t i = 0; i < nn; ++i) {
-    const uint32_t w0 = w[2 * i], w1 = w[2 * i + 1];
-    if ((w1 & 3u) == 3u) {  // leaf
-      const uint64_t cnt = w1 >> 2;
-      if ((cnt == 1 && w0 >= nprims) || (cnt > 1 && (uint64_t)w0 + cnt > nleaf)) {
-        *err = "kd-tree leaf " + std::to_string(i) + " references out of range";
-        return -1;
-      }
-      continue;
-    }
-    const uint64_t r = w1 >> 2;
-    if (i + 1 >= nn || r <= i + 1 || r >= nn) {
-      *err = "kd-tree node " + std::to_string(i) + " has a child out of order or range";
-      return -1;
-    }
-    for (const uint64_t c : {(uint64_t)i + 1, r}) {
-      if (++parents[c] > 1) {
-        *err = "kd-tree node " + std::to_string(c) + " has two parents";
-        return -1;
-      }
-      if (depth[i] >= kMaxTreeDepth) {
-        *err = "kd-tree deeper than 64 levels (KD_MAX_STACK)";
-        return -1;
-      }
-      depth[c] = (uint8_t)(depth[i] + 1);  // parents precede children: one forward pass
-      maxd = std::max(maxd, (int)depth[c]);
-    }
-  }
-  for (size_t i = 1; i < nn; ++i)
-    if (parents[i] != 1) {
-      *err = "kd-tree node " + std::to_string(i) + " is unreachable";
-      return -1;
-    }
-  return maxd;
-}
-
-// Traversal bounds of the resident tree (tree_depth): descents and stacks of
-// a valid traversal stay within depth + 2 (depth_cap); the per-lane overflow
-// area holds one descent's pushes beyond that, so a corrupt tree never
-// writes outside it (stack_depth).
-void set_tree_bounds(yk_device* d, int depth) {
-  d->max_depth = depth;
-  d->S.depth_cap = (unsigned)depth + 2u;
-}
-// a lane's stack is checked against depth_cap at every pop and every paused
-// descent, and one descent pushes at most two entries per trip of its
-// kDescTrips trips
-int stack_depth(const yk_device* d) { return (int)d->S.depth_cap + 2 * (int)kDescTrips + 2; }
-
-// YK_REFILL (1-64) overrides the per-scene refill threshold (set_handout);
-// 0 = none
-int refill_env() {
-  static const int v = [] {
-    const char* e = std::getenv("YK_REFILL");
-    const int r = e ? std::atoi(e) : 0;
-    return (r >= 1 && r <= 64) ? r : 0;
-  }();
-  return v;
-}
-
-// Enqueues one persistent traversal launch; no host synchronisation.
-// work: 128 zeroed words (per-XCD segment counters); acc: this kernel kind's
-// accumulators {nodes, triangle tests, errors, rays}. ev: timing pair or null.
-// RaySrc of whole 32-B rays / of a batch's shadow slots
-inline RaySrc ray_src(const yk_ray* r) { return RaySrc{r, nullptr, nullptr, 0u, 0u, 0u}; }
-inline RaySrc shadow_src(const Batch& B) {
-  if (!B.split) return ray_src(reinterpret_cast<const yk_ray*>(B.s_dir));
-  return RaySrc{nullptr, B.s_dir, B.s_dir + (long long)B.K * B.kstride, (1u << B.kshift) - 1u, (unsigned)B.kshift,
-                (unsigned)B.kstride};
-}
-
-// Camera rays take the group hand-out kernels (trace_body GROUP);
-// YK_CAMERA_GROUPS=0 (read per render: A/B runs, tests) keeps them on the
-// closest-hit kernels of the bounce rays
-bool camera_groups() {
-  const char* e = std::getenv("YK_CAMERA_GROUPS");
-  return !(e && std::atoi(e) == 0);
-}
-
-// The kernel a trace runs: small scenes (not with big leaves) the LDS-copy
-// kernels, big-leaf trees the BIG ones, universal scenes their own any-hit
-// kernels; split: a render batch's shadow slots in the split form (never
-// universal or big-leaf: shadow_split); camera: a render batch's camera rays.
-TraceVariant trace_variant(const yk_device* d, bool closest, bool split, bool camera = false) {
-  const bool small = d->small && !d->big_leaves;
-  if (closest && camera) return small ? kCameraSmall : d->big_leaves ? kCameraBig : kCamera;
-  if (split) return small ? kShadowSmallSplit : kShadowSplit;
-  if (small) return closest ? kClosestSmall : d->S.uni ? kShadowUniSmall : kShadowSmall;
-  if (closest) return d->big_leaves ? kClosestBig : kClosest;
-  if (d->S.uni) return d->big_leaves ? kShadowBigUni : kShadowUni;
-  return d->big_leaves ? kShadowBig : kShadow;
-}
-
-// per_cu of the variants with / without dynamic LDS (install_traversal once
-// small_bytes is known / yk_device_open)
-void fill_trace_occupancy(yk_device* d, bool dyn_lds) {
-  for (int v = 0; v < kTraceVariants; ++v) {
-    const TraceInfo& t = kTrace[v];
-    if (t.dyn_lds != dyn_lds) continue;
-    int blocks = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, t.kernel, 64 * t.waves,
-                                                        dyn_lds ? d->small_bytes : 0));
-    d->per_cu[v] = std::max(1, blocks);
-  }
-  if (dyn_lds) return;
-  // on large trees the universal any-hit kernels run on the plain ones' grids
-  d->per_cu[kShadowUni] = d->per_cu[kShadow];
-  d->per_cu[kShadowBigUni] = d->per_cu[kShadowBig];
-}
-
-template <bool CLOSEST>
-void enqueue_trace(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayCount n, yk_hit* hits,
-                   uint8_t* occ, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0, hipEvent_t ev1,
-                   bool camera = false) {
-  const TraceVariant v = trace_variant(d, CLOSEST, !CLOSEST && rays.rays == nullptr, camera);
-  const TraceInfo& t = kTrace[v];
-  const long long grid = (long long)d->cus * d->per_cu[v];
-  const int ovf_depth = std::max(1, stack_depth(d) - t.ring);
-  P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64 * t.waves);
-  if (ev0) HIPCHK(hipEventRecord(ev0, P.stream));
-  launch(t.kernel, (unsigned)grid, 64 * t.waves, t.dyn_lds ? d->small_bytes : 0, P.stream, d->S, rays, idx, n, hits,
-         occ, work, acc, P.ovf.p, ovf_depth, CLOSEST ? d->refill : d->refill_shadow);
-  if (ev1) HIPCHK(hipEventRecord(ev1, P.stream));
-}
-
-// Transparent-shadow any-hit launch (k_trace_shadow_ts): occlusion + filter.
-void enqueue_trace_ts(yk_device* d, Pipe& P, RaySrc rays, const unsigned* idx, RayCount n, uint8_t* occ,
-                      float* filt, int max_depth, unsigned long long* work, unsigned long long* acc, hipEvent_t ev0,
-                      hipEvent_t ev1) {
-  const long long grid = (long long)d->cus * (d->ts_glass ? d->per_cu_ts_glass : d->per_cu_ts);
-  const int ovf_depth = std::max(1, stack_depth(d) - kStackLds);
-  P.ovf.ensure((size_t)ovf_depth * (size_t)grid * 64);
-  if (ev0) HIPCHK(hipEventRecord(ev0, P.stream));
-  launch(d->ts_glass ? k_trace_shadow_ts_glass : k_trace_shadow_ts, (unsigned)grid, 64, 0, P.stream, d->S, rays, idx, n,
-         occ, filt, max_depth, work, acc, P.ovf.p, ovf_depth, d->refill_shadow);
-  if (ev1) HIPCHK(hipEventRecord(ev1, P.stream));
-}
-
-// k_pm_lookup keeps its stack in LDS (6 B per entry, depth entries per lane)
-// for radiance trees of < 2^16 nodes and depth <= kLdsPStack; else scratch.
-bool lookup_lds(const yk_device* d) { return d->rm_depth <= kLdsPStack && d->rm_nnodes < 65536; }
-size_t lookup_lds_bytes(int depth) { return (size_t)std::max(1, depth) * 64 * (sizeof(float) + sizeof(unsigned short)); }
-
-// Shadow rays as direction records + one origin per shading point (Batch
-// comment) when the lights take several samples (K >= 4) and the scene runs
-// the kernels that have the split form (not universal, big-leaf or
-// transparent-shadow); YK_SPLIT=0/1 (read per render: A/B runs, tests)
-// forces either form where it exists
-// Direct lighting's ambient occlusion: ao_samples more slots per shading
-// point. They take the split form with the lights' slots: every AO ray of a
-// point shares its origin and bias, so 32 rays are 32 * 16 + 16 B, not 32 * 32.
-inline int ao_slots(const yk_render_params* p) {
-  return (p->integrator == YK_INTEGRATOR_DIRECT && p->do_ao) ? std::max(0, p->ao_samples) : 0;
-}
-bool shadow_split(const yk_device* d, const yk_render_params* p) {
-  const char* e = std::getenv("YK_SPLIT");
-  const long long K = std::max<long long>(1, (long long)d->sum_light_slots + ao_slots(p));
-  return (e ? std::atoi(e) != 0 : K >= 4) && !d->S.uni && !d->big_leaves && !p->transp_shadows;
-}
-
-// One kernel kind's share of yk_stats.
-void add_trace_stats(yk_stats* st, bool closest, uint64_t rays, uint64_t nodes, uint64_t tris, double ms,
-                     uint64_t launches = 1) {
-  if (closest) {
-    st->closest_rays += rays;
-    st->closest_nodes += nodes;
-    st->closest_tris += tris;
-    st->ms_closest += ms;
-    st->closest_launches += launches;
-  } else {
-    st->shadow_rays += rays;
-    st->shadow_nodes += nodes;
-    st->shadow_tris += tris;
-    st->ms_shadow += ms;
-    st->shadow_launches += launches;
-  }
-}
-
-// Ray-query entry points: one launch, synchronised, statistics added to st.
-// filt: the transparent-shadow query (k_trace_shadow_ts, up to ts_depth surfaces).
-template <bool CLOSEST>
-void launch_trace(yk_device* d, Pipe& P, const yk_ray* rays, long long n, yk_hit* hits, uint8_t* occ, yk_stats* st,
-                  float* filt = nullptr, int ts_depth = 0) {
-  if (n <= 0) return;
-  if (n > 0x7FFFFFFFll - (1ll << 24)) throw std::invalid_argument("ray batch too large (max ~2^31 rays per call)");
-  unsigned long long* work = P.counters.p;
-  unsigned long long* acc = P.counters.p + 128;
-  HIPCHK(hipMemsetAsync(work, 0, 144 * sizeof(unsigned long long), P.stream));
-#ifdef YK_TRAV_STATS
-  {
-    const unsigned long long z = 0;
-    HIPCHK(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_spill_stores), &z, sizeof z, 0, hipMemcpyHostToDevice, P.stream));
-  }
-#endif
-  const RayCount cnt{nullptr, 0, n};
-  if (filt) enqueue_trace_ts(d, P, ray_src(rays), nullptr, cnt, occ, filt, ts_depth, work, acc, P.ev0, P.ev1);
-  else enqueue_trace<CLOSEST>(d, P, ray_src(rays), nullptr, cnt, hits, occ, work, acc, P.ev0, P.ev1);
-  unsigned long long h[13];
-  HIPCHK(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, P.stream));
-  HIPCHK(hipStreamSynchronize(P.stream));
-  if (h[2]) throw watchdog_error("kd-tree traversal watchdog fired on " + std::to_string(h[2]) + " rays");
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, P.ev0, P.ev1));
-#ifdef YK_TRAV_STATS
-  std::fprintf(stderr,
-               "[trav-stats] %s rays %lld: wave iterations %llu, active lanes/iter %.2f, descent trips max %.2f / "
-               "mean-active %.2f, leaf trips max %.2f / mean-active %.2f, refills %llu (%.1f rays each)\n",
-               CLOSEST ? "closest" : "shadow", n, h[4], (double)h[5] / (double)h[4], (double)h[6] / (double)h[4],
-               (double)h[0] / (double)h[5], (double)h[7] / (double)h[4], (double)h[1] / (double)h[5], h[8],
-               (double)n / (double)h[8]);
-  {
-    const double tot = (double)(h[9] + h[10] + h[11] + h[12]);
-    std::fprintf(stderr, "[trav-stats] %s cycles: refill %.1f%% descent %.1f%% leaf %.1f%% pop %.1f%%; per wave iteration %.0f\n",
-                 CLOSEST ? "closest" : "shadow", 100.0 * h[9] / tot, 100.0 * h[10] / tot, 100.0 * h[11] / tot,
-                 100.0 * h[12] / tot, tot / (double)h[4]);
-    unsigned long long sp = 0;
-    HIPCHK(hipMemcpyFromSymbol(&sp, HIP_SYMBOL(g_spill_stores), sizeof sp));
-    std::fprintf(stderr, "[trav-stats] %s overflow-area stores %llu (%.3f per ray, %.1f MB at 8 B each)\n",
-                 CLOSEST ? "closest" : "shadow", sp, (double)sp / (double)n, 8e-6 * (double)sp);
-  }
-#endif
-  if (st) add_trace_stats(st, CLOSEST, (uint64_t)n, h[0], h[1], ms);
-}
-
-}  // namespace
-
+#include "yk_pipe_host.inc"    // HIPCHK, DBuf, launch, Pipe, pipes_env, plan_batches
+#include "yk_device_host.inc"  // kTrace, kShade, struct yk_device, bind_constants, YK_GUARD_*
+#include "yk_trace_host.inc"   // tree_depth, trace_variant, enqueue_trace*, launch_trace, yk_trace_*
 #include "yk_upload_host.inc"  // make_*, upload_qmc, install_traversal, yk_device_open / close, yk_device_upload
-
-extern "C" {
-
-int yk_trace_closest(yk_device* d, const yk_ray* d_rays, int64_t n, yk_hit* d_hits, yk_stats* st) {
-  if (!d || (n > 0 && (!d_rays || !d_hits)) || n < 0) return set_error(YK_ERR_ARG, "yk_trace_closest: bad arguments");
-  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_trace_closest: no scene uploaded");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  yk_stats local{};
-  launch_trace<true>(d, d->pipe[0], d_rays, n, d_hits, nullptr, st ? st : &local);
-  return YK_OK;
-  YK_GUARD_END
-}
-
-int yk_trace_shadow(yk_device* d, const yk_ray* d_rays, int64_t n, uint8_t* d_occ, yk_stats* st) {
-  if (!d || (n > 0 && (!d_rays || !d_occ)) || n < 0) return set_error(YK_ERR_ARG, "yk_trace_shadow: bad arguments");
-  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_trace_shadow: no scene uploaded");
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  yk_stats local{};
-  launch_trace<false>(d, d->pipe[0], d_rays, n, nullptr, d_occ, st ? st : &local);
-  return YK_OK;
-  YK_GUARD_END
-}
-
-int yk_trace_shadow_filtered(yk_device* d, const yk_ray* d_rays, int64_t n, uint8_t* d_occ, float* d_filter,
-                             int32_t max_depth, yk_stats* st) {
-  if (!d || (n > 0 && (!d_rays || !d_occ || !d_filter)) || n < 0)
-    return set_error(YK_ERR_ARG, "yk_trace_shadow_filtered: bad arguments");
-  if (max_depth < 0 || max_depth > 8) return set_error(YK_ERR_UNSUPPORTED, "max_depth must be in [0, 8]");
-  if (!d->uploaded) return set_error(YK_ERR_STATE, "yk_trace_shadow_filtered: no scene uploaded");
-  if (n <= 0) return YK_OK;
-  YK_GUARD_BEGIN
-  HIPCHK(hipSetDevice(d->ordinal));
-  bind_constants(d);  // the transparent-shadow leaf body reads the materials
-  launch_trace<false>(d, d->pipe[0], d_rays, n, nullptr, d_occ, st, d_filter, max_depth);
-  return YK_OK;
-  YK_GUARD_END
-}
-
-// Filter functions of imageFilm_t (imagefilm.cc:81-123), in the survey
-// build's compiled forms: Gauss folds -6*log2(e) into one constant and drops
-// fExp2's upper clamp (the argument is never positive); Lanczos2 uses the
-// FAST_TRIG fSin (yk::host_fsin) on (float)(x*pi) and (float)(x*pi/2).
-// fExp2, mathOptimizations.h:100-114 (POLYEXP :85); pinned bit for bit to
-// the reference's own fExp2 compiled in the build container
-// (oracle/ref_check.cc, tests/test_ref_pinning.py through yk_debug_qmc_probe)
-static float host_fexp2(float x) {
-  x = (x < 129.00000f) ? x : 129.00000f;    // f_HI
-  x = (x > -126.99999f) ? x : -126.99999f;  // f_LOW
-  const int ip = (int)(x - 0.5f);
-  const float fp = x - (float)ip;
-  const uint32_t eb = (uint32_t)(ip + 127) << 23;
-  float e;
-  std::memcpy(&e, &eb, 4);
-  const float poly = ((((1.8775767e-3f * fp + 8.9893397e-3f) * fp + 5.5826318e-2f) * fp + 2.4015361e-1f) * fp +
-                      6.9315308e-1f) * fp + 9.9999994e-1f;
-  return e * poly;
-}
-static float filter_gauss(float dx, float dy) {
-  const float r2 = dx * dx + dy * dy;
-  float k;
-  const uint32_t kbits = 0xc10a7facu;  // (float)(-6 * (float)M_LOG2E)
-  std::memcpy(&k, &kbits, 4);
-  // r2 * k <= 0: the upper clamp the compiled form drops is a no-op
-  const float v = (float)((double)host_fexp2(r2 * k) - 0.00247875);
-  return (v > 0.f) ? v : 0.f;
-}
-static float filter_lanczos(float dx, float dy) {
-  const float x = std::sqrt(dx * dx + dy * dy);
-  if (x == 0.f) return 1.f;
-  if (!(x > -2.f) || !(x < 2.f)) return 0.f;
-  const float a = (float)((double)x * YK_PI_D);
-  const float b = (float)((double)x * (YK_PI_D * 0.5));
-  return (host_fsin(b) * host_fsin(a)) / (a * b);
-}
-
-static FilmConst make_film(const yk_render_params* p) {
-  FilmConst F{};
-  F.cx0 = p->xstart;
-  F.cy0 = p->ystart;
-  F.w = p->width;
-  F.h = p->height;
-  F.cx1 = p->xstart + p->width;
-  F.cy1 = p->ystart + p->height;
-  F.tile = p->tile_size > 0 ? p->tile_size : 32;
-  F.ntx = (p->width + F.tile - 1) / F.tile;
-  float fw = (float)((double)p->aa_pixelwidth * 0.5);
-  if (p->filter == YK_FILTER_MITCHELL) fw *= 2.6f;
-  else if (p->filter == YK_FILTER_GAUSS) fw *= 2.f;
-  if (fw < 0.501f) fw = 0.501f;
-  if (fw > 4.f) fw = 4.f;
-  if (p->filter_width > 0.f) fw = p->filter_width;  // the live film's filterw (yk_film_filter_from_table)
-  F.filterw = fw;
-  F.tableScale = 0.9999 * 16 / F.filterw;
-  auto r2i = [](double v) { return (int)(v + (0.5 - 1.4e-11)); };
-  // target - source offsets reachable by Round2Int extents for dx in [0,1)
-  F.olo_x = F.olo_y = r2i(0.0 - fw);
-  F.ohi_x = F.ohi_y = r2i(1.0 + fw - 1.0);
-  const float scale = 1.f / 16.f;
-  for (int y = 0; y < 16; ++y)
-    for (int x = 0; x < 16; ++x) {
-      const float fx = (x + .5f) * scale, fy = (y + .5f) * scale;
-      float v = 1.f;
-      if (p->filter == YK_FILTER_MITCHELL) {
-        const float xx = 2.f * std::sqrt(fx * fx + fy * fy);
-        if (xx >= 2.f) v = 0.f;
-        else if (xx >= 1.f) v = (float)(xx * (xx * (xx * -0.38888889f + 2.0f) - 3.33333333f) + 1.77777778f);
-        else v = (float)(xx * xx * (1.16666666f * xx - 2.0f) + 0.88888889f);
-      } else if (p->filter == YK_FILTER_GAUSS) {
-        v = filter_gauss(fx, fy);
-      } else if (p->filter == YK_FILTER_LANCZOS) {
-        v = filter_lanczos(fx, fy);
-      }
-      F.table[y * 16 + x] = v;
-    }
-  F.spp = p->aa_samples > 0 ? p->aa_samples : 1;
-  F.d1 = (float)(1.0 / (double)(float)F.spp);
-  return F;
-}
-
-int yk_film_filter_from_table(const float* table, float filterw, yk_render_params* p) {
-  if (!table || !p) return set_error(YK_ERR_ARG, "yk_film_filter_from_table: NULL argument");
-  if (!(filterw >= 0.501f && filterw <= 4.f))
-    return set_error(YK_ERR_UNSUPPORTED, "film filterw outside [0.501, 4] (imagefilm.cc:150)");
-  for (int f : {YK_FILTER_BOX, YK_FILTER_MITCHELL, YK_FILTER_GAUSS, YK_FILTER_LANCZOS}) {
-    yk_render_params q = *p;
-    q.filter = f;
-    const FilmConst F = make_film(&q);
-    if (std::memcmp(F.table, table, sizeof F.table) == 0) {
-      p->filter = f;
-      p->filter_width = filterw;
-      return YK_OK;
-    }
-  }
-  return set_error(YK_ERR_UNSUPPORTED, "film filter table is none of box / Mitchell / Gauss / Lanczos2");
-}
-
-}  // extern "C"
-
+#include "yk_film_host.inc"    // the film filter tables, make_film, yk_film_filter_from_table
 #include "yk_photon_host.inc"
 #include "yk_kdtree_gpu.inc"
 #include "yk_render_host.inc"

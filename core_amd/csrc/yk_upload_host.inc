@@ -1,9 +1,10 @@
 // Scene upload (included by yk_device.hip): the record builders make_cam /
 // make_*_light / make_mat, upload_qmc, the traversal copies of the resident
 // tree (install_traversal), yk_device_open / close / sync and
-// yk_device_upload with its steps. Depends on yk_pipe_host.inc and, in
-// yk_device.hip ahead of the include, on struct yk_device, bind_constants,
-// the YK_GUARD_* macros, tree_depth, set_tree_bounds and fill_trace_occupancy.
+// yk_device_upload with its steps. Depends on yk_pipe_host.inc, on
+// yk_device_host.inc (struct yk_device, bind_constants, the YK_GUARD_*
+// macros) and on yk_trace_host.inc (tree_depth, set_tree_bounds,
+// fill_trace_occupancy).
 
 namespace {
 

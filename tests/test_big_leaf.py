@@ -19,18 +19,22 @@ N_DUP = 70000
 _CACHE = {}
 
 
-def big_leaf_scene(res=24):
-    if res not in _CACHE:
+def big_leaf_scene(res=24, mode=A.YK_MODE_TRIANGLE):
+    if (res, mode) not in _CACHE:
         s = Scene()
         p = s.generate("cornell_pt", res, res)
         tri = np.array([[-0.3, 0.5, 0.1], [0.3, 0.5, 0.1], [0.0, 1.1, 0.1],
                         [-0.3, 0.6, 0.0], [0.3, 0.6, 0.2], [0.0, 1.0, 0.15],
                         [-0.25, 0.55, 0.3], [0.32, 0.7, -0.1], [0.05, 1.05, 0.05]], np.float32)
         faces = np.tile(np.array([[0, 1, 2], [3, 4, 5], [6, 7, 8]], np.int32), (N_DUP, 1))
-        s.add_mesh(tri, faces, 0)
+        mid = s.add_mesh(tri, faces, 0)
+        if mode == A.YK_MODE_UNIVERSAL:
+            s.set_mode(mode)
+            for oid in range(1, mid + 1):
+                s.set_mesh_type(oid, A.YK_MESH_VTRIM)
         s.build()
-        _CACHE[res] = (s, p)
-    return _CACHE[res]
+        _CACHE[(res, mode)] = (s, p)
+    return _CACHE[(res, mode)]
 
 
 def _largest_leaf(s):
@@ -81,6 +85,28 @@ def test_big_leaf_traversal_bit_exact(gpu_device):
     sh[::2, 7] = np.abs(sh[::2, 7]) + 0.3
     sh[1::4, 7] = 0.6
     occ, cnt = orc.shadow(sh)
+    st = A.yk_stats()
+    gocc = gpu_device.trace_shadow(gpu_device.rays_to_device(sh), st).cpu().numpy()
+    assert (gocc == occ).all(), f"{(gocc != occ).sum()} mismatches"
+    assert 0 < occ.sum() < len(occ)
+    assert st.shadow_nodes == cnt[0] and st.shadow_tris == cnt[1]
+
+
+@pytest.mark.gpu
+def test_big_leaf_universal_any_hit_bit_exact(gpu_device):
+    """The same fixture as a universal-mode scene: the one tree that runs
+    k_trace_shadow_big_uni (relative owner keys and t > tmin together).
+    Occlusion and the reference's node and test counts, against the oracle."""
+    from oracle.oracle import Oracle
+    s, _ = big_leaf_scene(mode=A.YK_MODE_UNIVERSAL)
+    assert _largest_leaf(s) >= 1 << 17
+    orc = Oracle(s)
+    sh = _rays(s, n_aim=300, n_rand=100)
+    sh[:, 6] = 0.05  # as test_universal: a tmin at which t > tmin and t >= 0 can differ
+    sh[::2, 7] = np.abs(sh[::2, 7]) + 0.3
+    sh[1::4, 7] = 0.6
+    occ, cnt = orc.shadow(sh)
+    gpu_device.upload(s)
     st = A.yk_stats()
     gocc = gpu_device.trace_shadow(gpu_device.rays_to_device(sh), st).cpu().numpy()
     assert (gocc == occ).all(), f"{(gocc != occ).sum()} mismatches"

@@ -1,5 +1,5 @@
-"""Every cell of the shading-kernel table (kShade, yk_device.hip): material
-level {diffuse-only, general, glossy, coated} x light level {area light only,
+"""Every cell of the shading-kernel table (kShade, yk_device_host.inc):
+material level {diffuse-only, general, glossy, coated} x light level {area light only,
 + a spot light, + a mesh light}, under integrator settings that between them
 launch every kernel the table holds.
 
