@@ -1,6 +1,6 @@
 // The device handle and its kernel tables (included by yk_device.hip after
 // yk_pipe_host.inc): TraceVariant and kTrace, expanded from the list
-// YK_TRACE_VARIANTS of yk_device.hip's traversal section; ShadeVariant,
+// YK_TRACE_VARIANTS of yk_trav.inc; ShadeVariant,
 // ShadeKernels, shade_cell and kShade with its static_asserts; struct
 // yk_device and shade_kernels; the constant-memory binding (bind_constants,
 // same_constants); watchdog_error and the YK_GUARD_* macros. Depends on the
@@ -8,7 +8,7 @@
 // DBuf, Pipe).
 
 // The trace kernels of one signature, as a table: the enumerators and the
-// rows both come from YK_TRACE_VARIANTS (yk_device.hip, traversal section),
+// rows both come from YK_TRACE_VARIANTS (yk_trav.inc),
 // in its order. k_trace_shadow_ts takes two more arguments (filter colours,
 // depth) and stays on its own (enqueue_trace_ts, per_cu_ts).
 enum TraceVariant {

@@ -1,4 +1,5 @@
-// Trace launches (included by yk_device.hip after yk_device_host.inc): the
+// Trace launches, the host counterpart of yk_trav.inc's kernels (included
+// by yk_device.hip after yk_device_host.inc): the
 // tree check and traversal bounds (tree_depth, set_tree_bounds, stack_depth),
 // the choice and sizing of a trace kernel (trace_variant,
 // fill_trace_occupancy), enqueue_trace / enqueue_trace_ts, shadow_split,
