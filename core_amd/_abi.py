@@ -20,6 +20,7 @@ YK_MAT_GLASS = 5
 YK_LIGHT_AREA, YK_LIGHT_POINT, YK_LIGHT_DIRECTIONAL, YK_LIGHT_SPOT, YK_LIGHT_SPHERE = 0, 1, 2, 3, 4
 YK_LIGHT_MESH = 5
 YK_LIGHT_SUN = 6
+YK_LIGHT_BACKGROUND = 7
 YK_MESH_LIGHT_MAX_TRIS, YK_MESH_LIGHT_MAX_DEPTH = 65536, 29
 YK_MESH_SMOOTH, YK_MESH_NORMALS_EXPORTED = 1, 2
 YK_INTEGRATOR_DIRECT, YK_INTEGRATOR_PATH, YK_INTEGRATOR_PHOTON = 0, 1, 2
@@ -116,6 +117,16 @@ class yk_sphere_light_state(C.Structure):
 class yk_sun_light_state(C.Structure):
     _fields_ = [("color", f3), ("col_pdf", f3), ("direction", f3), ("du", f3), ("dv", f3),
                 ("pdf", C.c_float), ("invpdf", C.c_float), ("cos_angle", C.c_double), ("samples", C.c_int32)]
+
+
+class yk_gradient_background(C.Structure):
+    _fields_ = [("horizon_color", f3), ("zenith_color", f3), ("horizon_ground_color", f3),
+                ("zenith_ground_color", f3), ("power", C.c_float)]
+
+
+class yk_background_light(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("shoot_caustics", C.c_int32), ("shoot_diffuse", C.c_int32),
+                ("abs_intersect", C.c_int32)]
 
 
 class yk_mesh_light(C.Structure):
@@ -284,6 +295,11 @@ SIGNATURES = {
     "yk_scene_set_mesh_light_color": (C.c_int, [P, i32, fp]),
     "yk_scene_set_background": (C.c_int, [P, fp, C.c_float]),
     "yk_scene_get_background": (C.c_int, [P, fp, i32p]),
+    "yk_scene_set_gradient_background": (C.c_int, [P, C.POINTER(yk_gradient_background)]),
+    "yk_scene_get_gradient_background": (C.c_int, [P, C.POINTER(yk_gradient_background), i32p]),
+    "yk_scene_add_background_light": (C.c_int, [P, C.POINTER(yk_background_light)]),
+    "yk_scene_get_background_light": (C.c_int, [P, i32, C.POINTER(yk_background_light)]),
+    "yk_scene_export_background_light": (C.c_int, [P, i32, i32p, i32p, i32p, i32p, fp, fp, fp, fp, fp, fp, fp]),
     "yk_scene_get_camera_state": (C.c_int, [P, C.POINTER(yk_camera_state)]),
     "yk_scene_generate": (C.c_int, [P, C.c_char_p, i32, i32, i32, i32, C.POINTER(yk_render_params)]),
     "yk_render_params_default": (None, [C.POINTER(yk_render_params)]),

@@ -305,6 +305,7 @@ int light_slots(const Scene& s, size_t i) {
     case YK_LIGHT_SPHERE: return s.sphere_states[i].samples;  // canIntersect() is false: no MIS half
     case YK_LIGHT_MESH: return 2 * s.mesh_lights[i].params.samples;  // canIntersect(): light + BSDF halves
     case YK_LIGHT_SUN: return 2 * s.sun_states[i].samples;           // canIntersect(): light + BSDF halves
+    case YK_LIGHT_BACKGROUND: return 2 * s.bg_lights[i].params.samples;  // canIntersect() (bglight.h:47)
     default: return 1;
   }
 }
@@ -422,6 +423,7 @@ void Scene::add_light(const yk_light& l) {
   sphere_states.push_back(l.type == YK_LIGHT_SPHERE ? sphere_state(l) : yk_sphere_light_state{});
   mesh_lights.emplace_back();
   sun_states.push_back(l.type == YK_LIGHT_SUN ? sun_state(l) : yk_sun_light_state{});
+  bg_lights.emplace_back();
 }
 void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   lights.push_back(yk_light{});
@@ -435,6 +437,7 @@ void Scene::add_dirac_light_state(const yk_dirac_light_state& l) {
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
   sun_states.push_back(yk_sun_light_state{});
+  bg_lights.emplace_back();
 }
 void Scene::add_light_state(const yk_area_light_state& l) {
   lights.push_back(yk_light{});
@@ -446,6 +449,7 @@ void Scene::add_light_state(const yk_area_light_state& l) {
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
   sun_states.push_back(yk_sun_light_state{});
+  bg_lights.emplace_back();
 }
 void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   lights.push_back(yk_light{});
@@ -459,6 +463,7 @@ void Scene::add_spot_light_state(const yk_spot_light_state& l) {
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
   sun_states.push_back(yk_sun_light_state{});
+  bg_lights.emplace_back();
 }
 void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   lights.push_back(yk_light{});
@@ -472,6 +477,7 @@ void Scene::add_sphere_light_state(const yk_sphere_light_state& l) {
   sphere_states.push_back(l);
   mesh_lights.emplace_back();
   sun_states.push_back(yk_sun_light_state{});
+  bg_lights.emplace_back();
 }
 void Scene::add_sun_light_state(const yk_sun_light_state& l) {
   lights.push_back(yk_light{});
@@ -485,6 +491,7 @@ void Scene::add_sun_light_state(const yk_sun_light_state& l) {
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.emplace_back();
   sun_states.push_back(l);
+  bg_lights.emplace_back();
 }
 // meshLight_t::factory (meshlight.cc:221-236): color * (CFLOAT)power * M_PI,
 // both through color_t's operator*(color_t, CFLOAT): float products
@@ -510,7 +517,47 @@ void Scene::add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int n
   sphere_states.push_back(yk_sphere_light_state{});
   mesh_lights.push_back(std::move(m));
   sun_states.push_back(yk_sun_light_state{});
+  bg_lights.emplace_back();
   built = false;
+}
+void Scene::add_background_light(const yk_background_light& l) {
+  BgLight b;
+  b.params = l;
+  b.params.shoot_caustics = l.shoot_caustics ? 1 : 0;
+  b.params.shoot_diffuse = l.shoot_diffuse ? 1 : 0;
+  b.params.abs_intersect = l.abs_intersect ? 1 : 0;
+  b.present = true;
+  yk_light p{};
+  p.type = YK_LIGHT_BACKGROUND;
+  p.samples = l.samples;
+  lights.push_back(p);
+  light_has_params.push_back(false);
+  light_kind.push_back(YK_LIGHT_BACKGROUND);
+  yk_area_light_state a{};
+  a.samples = 1;
+  light_states.push_back(a);
+  dirac_states.push_back(yk_dirac_light_state{});
+  spot_states.push_back(yk_spot_light_state{});
+  sphere_states.push_back(yk_sphere_light_state{});
+  mesh_lights.emplace_back();
+  sun_states.push_back(yk_sun_light_state{});
+  bg_lights.push_back(std::move(b));
+  built = false;
+}
+// gradientBackground_t::factory (gradientback.cc:83-97): each colour times power
+void Scene::set_gradient_background(const yk_gradient_background* g) {
+  has_gradient = g != nullptr;
+  gradient_params = g ? *g : yk_gradient_background{};
+  for (int k = 0; k < 3; ++k) {
+    gradient[k] = g ? g->zenith_color[k] * g->power : 0.f;
+    gradient[3 + k] = g ? g->horizon_color[k] * g->power : 0.f;
+    gradient[6 + k] = g ? g->zenith_ground_color[k] * g->power : 0.f;
+    gradient[9 + k] = g ? g->horizon_ground_color[k] * g->power : 0.f;
+  }
+  if (g) {
+    has_background = false;
+    for (float& x : background) x = 0.f;
+  }
 }
 void Scene::set_camera(const yk_camera& c) {
   camera = c;
@@ -633,6 +680,85 @@ static void init_mesh_light(const Scene& S, MeshLight& L) {
   build_kdtree(L.verts.data(), n, L.tree, -1, 1, 0.8f, 0.33f);
 }
 
+void background_eval(int kind, const float* constant, const float* grad, const float* dir, float* rgb) {
+  if (kind != YK_BG_GRADIENT) {
+    for (int k = 0; k < 3; ++k) rgb[k] = constant[k];
+    return;
+  }
+  float blend = dir[2];
+  const float* z = grad;
+  if (!(blend >= 0.f)) {
+    blend = -blend;
+    z = grad + 6;
+  }
+  for (int k = 0; k < 3; ++k) rgb[k] = blend * z[k] + (1.f - blend) * z[3 + k];
+  if (std::min(rgb[0], std::min(rgb[1], rgb[2])) < 1e-6f) rgb[0] = rgb[1] = rgb[2] = 1e-5f;
+}
+
+// pdf1D_t's constructor (sample_utils.h:109-118) with CumulateStep1dDF (:85-98):
+// the double running total, cdf[i] = float(c), integral = (float)c, then each
+// cdf entry divided by the float integral
+static void pdf1d(const float* f, int n, float* cdf, float& integral, float& inv_integral) {
+  double c = 0.0;
+  const double delta = 1.0 / (double)n;
+  cdf[0] = 0.f;
+  for (int i = 1; i < n + 1; ++i) {
+    c += (double)f[i - 1] * delta;
+    cdf[i] = (float)c;
+  }
+  integral = (float)c;
+  for (int i = 1; i < n + 1; ++i) cdf[i] /= integral;
+  inv_integral = 1.f / integral;
+}
+
+// bgLight_t::init (bglight.cc:68-118) up to the tables, source order:
+// MAX_VSAMPLES rows; per row fy = (y + 0.5f) * inv, sintheta = fSin of the
+// double fy * M_PI narrowed at the call, nu = MIN_SAMPLES + (int)(sintheta *
+// (MAX_USAMPLES - MIN_SAMPLES)) columns of eval(invSpheremap(fx, fy)).energy()
+// * sintheta; invSpheremap is texture.h:93-102 (theta = v * M_PI and phi =
+// -(u * M_2PI) are double products stored to float). The members taken from
+// the scene bound come at upload (make_bg_light).
+static void init_bg_light(const Scene& S, BgLight& L) {
+  constexpr int kMaxV = 360, kMaxU = 720, kMin = 16;
+  const int kind = S.background_kind();
+  const int nv = kMaxV;
+  const float inv = 1.f / (float)nv;
+  L.row_count.assign(nv, 0);
+  L.row_offset.assign(nv, 0);
+  L.row_integral.assign(nv, 0.f);
+  L.row_inv_integral.assign(nv, 0.f);
+  L.func_u.clear();
+  L.cdf_u.clear();
+  L.func_v.assign(nv, 0.f);
+  L.cdf_v.assign((size_t)nv + 1, 0.f);
+  float fu[kMaxU];
+  for (int y = 0; y < nv; ++y) {
+    const float fy = ((float)y + 0.5f) * inv;
+    const float sintheta = host_fsin((float)((double)fy * 3.14159265358979323846));
+    const int nu = kMin + (int)(sintheta * (float)(kMaxU - kMin));
+    const float inu = 1.f / (float)nu;
+    for (int x = 0; x < nu; ++x) {
+      const float fx = ((float)x + 0.5f) * inu;
+      const float theta = (float)((double)fy * 3.14159265358979323846);
+      const float phi = (float)-((double)fx * 6.28318530717958647692);
+      const float ct = host_fcos(theta), st = host_fsin(theta);
+      const float cp = host_fcos(phi), sp = host_fsin(phi);
+      const float dir[3] = {st * cp, st * sp, -ct};
+      float c[3];
+      background_eval(kind, S.background, S.gradient, dir, c);
+      fu[x] = (((c[0] + c[1]) + c[2]) * 0.333333f) * sintheta;  // color_t::energy(), color.h
+    }
+    L.row_count[y] = nu;
+    L.row_offset[y] = (int32_t)L.func_u.size();
+    L.func_u.insert(L.func_u.end(), fu, fu + nu);
+    const size_t at = L.cdf_u.size();
+    L.cdf_u.resize(at + (size_t)nu + 1);
+    pdf1d(fu, nu, &L.cdf_u[at], L.row_integral[y], L.row_inv_integral[y]);
+    L.func_v[y] = L.row_integral[y];
+  }
+  pdf1d(L.func_v.data(), nv, L.cdf_v.data(), L.v_integral, L.v_inv_integral);
+}
+
 void Scene::finalize() {
   // scene_t::update, scene.cc:755-782: visible non-base TRIM meshes and
   // instances in object id order, triangles in insertion order. Universal
@@ -705,6 +831,8 @@ void Scene::finalize() {
   build_kdtree(tri_verts.data(), ntris, tree);
   for (MeshLight& L : mesh_lights)
     if (!L.obj_ids.empty()) init_mesh_light(*this, L);
+  for (BgLight& L : bg_lights)
+    if (L.present) init_bg_light(*this, L);
   static std::atomic<uint64_t> next_generation{1};
   generation = next_generation.fetch_add(1);
   built = true;

@@ -48,6 +48,24 @@ struct MeshLight {
   KdTree tree;
 };
 
+// bgLight_t: parameters, and after finalize() the tables init() computes
+// (bglight.cc:68-118): one pdf1D_t per row (uDist[y]) and one over the rows'
+// integrals (vDist); a cdf holds count + 1 entries
+struct BgLight {
+  yk_background_light params{};
+  bool present = false;              // the entry is a background light (the others' entries stay empty)
+  std::vector<int32_t> row_count, row_offset;  // per row: count, first element in func_u
+  std::vector<float> row_integral, row_inv_integral;
+  std::vector<float> func_u, cdf_u;  // rows back to back: sum(count), sum(count) + nrows
+  std::vector<float> func_v, cdf_v;  // nrows, nrows + 1
+  float v_integral = 0.f, v_inv_integral = 0.f;
+};
+
+enum { YK_BG_NONE = 0, YK_BG_CONSTANT = 1, YK_BG_GRADIENT = 2 };  // Scene::background_kind()
+// background_t::eval of a scene's background (constBackground_t: the colour;
+// gradientBackground_t::eval, gradientback.cc:60-79); grad = szenith, shoriz, gzenith, ghoriz
+void background_eval(int kind, const float* constant, const float* grad, const float* dir, float* rgb);
+
 struct Scene {
   std::vector<Mesh> meshes;          // object-id order
   int mode = YK_MODE_TRIANGLE;       // scene_t::mode: which meshes the tree holds
@@ -68,8 +86,20 @@ struct Scene {
   std::vector<yk_sphere_light_state> sphere_states; // sphere lights (zero entry for every other kind)
   std::vector<MeshLight> mesh_lights;               // mesh lights (empty entry for every other kind)
   std::vector<yk_sun_light_state> sun_states;       // sun lights (zero entry for every other kind)
+  std::vector<BgLight> bg_lights;                   // background lights (empty entry for every other kind)
   bool has_background = false;
   float background[3] = {0.f, 0.f, 0.f};            // constBackground_t::color (color*power)
+  // gradientBackground_t: excludes the constant one. gradient_params as set;
+  // gradient = szenith, shoriz, gzenith, ghoriz, each times power (gradientback.cc:97)
+  bool has_gradient = false;
+  yk_gradient_background gradient_params{};
+  float gradient[12] = {};
+  int background_kind() const { return has_gradient ? YK_BG_GRADIENT : has_background ? YK_BG_CONSTANT : YK_BG_NONE; }
+  bool has_bg_light() const {
+    for (const int k : light_kind)
+      if (k == YK_LIGHT_BACKGROUND) return true;
+    return false;
+  }
   yk_camera_state camera_state{};
   bool has_camera = false;
 
@@ -82,6 +112,8 @@ struct Scene {
   void add_sphere_light_state(const yk_sphere_light_state& l);
   void add_sun_light_state(const yk_sun_light_state& l);
   void add_mesh_light(const yk_mesh_light& l, const int32_t* obj_ids, int nobj);
+  void add_background_light(const yk_background_light& l);
+  void set_gradient_background(const yk_gradient_background* g);
   void set_camera(const yk_camera& c);
   void set_camera_state(const yk_camera_state& c);
 

@@ -99,7 +99,26 @@ struct DMat {
 static_assert(sizeof(DMat) == 32 * sizeof(int), "DMat: the shading kernels' LDS copy is sized by it");
 
 struct DLight {  // areaLight_t members after its constructor (arealight.cc:30-49)
-  float corner[3], toX[3], toY[3], fnormal[3], c2[3], c3[3], c4[3], color[3];
+  // The record keeps its size and every member its offset: a background
+  // light's own members lie over the area light's corners, which it has not.
+  union {
+    struct {
+      float corner[3], toX[3], toY[3], fnormal[3], c2[3], c3[3], c4[3];
+    };
+    // bgLight_t (bglight.h:58-66) and the background it is bound to: kind
+    // (kBgConstant: `color` below holds constBackground_t::color; kBgGradient:
+    // grad = szenith, shoriz, gzenith, ghoriz), absInter, vDist->invIntegral and
+    // the tables' sum of row counts; the tables themselves lie behind
+    // DScene::ml[mesh].cdf (bg_tables). samples, soft = 1 (light_sampled) and,
+    // from init(scene), epos = worldCenter, wradius = worldRadius, area = aPdf.
+    struct {
+      float grad[12];
+      int kind, abs_inter;
+      float v_inv_integral;
+      int total_u;
+    } bg;
+  };
+  float color[3];
   float e2[3], e3[3], e4[3];  // c2 - corner, c3 - corner, c4 - corner: intersect()'s triangle edges
   float area;
   int samples;
@@ -1409,6 +1428,8 @@ __device__ __forceinline__ bool sun_hit(const DLight& L, v3 dir, float& t, float
   return true;
 }
 
+#include "yk_bglight.inc"
+
 // pdf1D_t::DSample (sample_utils.h:141-157): u == 0 answers 0; otherwise
 // std::lower_bound over cdf[0..n] (the first entry >= u), minus 1, clamped at 0
 __device__ __forceinline__ int mesh_dsample(const float* cdf, int n, float u) {
@@ -1806,12 +1827,13 @@ struct RenderConst {
   int integrator;
   int transp_bg;
   int nlights;
-  int has_bg;     // constant background color for camera-ray misses
+  int has_bg;     // the background a missing ray adds: kBgNone, kBgConstant (bg) or kBgGradient (bg_grad, at the end)
   float bg[3];
   float d1;       // 1/spp as renderTile computes it
   int pm_fg;      // photon mapping with final gathering: col += pathCol / nSampl at the finish
   int pm_showmap; // photon mapping show_map: no direct light
   int merged;     // merged shadow launch: pathCol lives in k_resolve_merged's registers from 0
+  float bg_grad[12];  // gradientBackground_t: szenith, shoriz, gzenith, ghoriz (bg_gradient)
 };
 
 // ------------------------------------------------------------ kernels
@@ -2157,9 +2179,10 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
 // slot with the contribution it adds when unoccluded. Returns #rays; sets bit
 // k of `traced` (k < 64) for each slot that holds a ray.
 // XL: kXLNone, kXLSpotSphere (the scene holds a spot or sphere light),
-// kXLMesh (it holds a mesh light; ml = DScene::ml) or kXLSun (it holds a sun
-// light); each level holds the code of those below it: see kShade
-constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2, kXLSun = 3;
+// kXLMesh (it holds a mesh light; ml = DScene::ml), kXLSun (it holds a sun
+// light) or kXLBg (it holds a background light, whose tables ml reaches too);
+// each level holds the code of those below it: see kShade
+constexpr int kXLNone = 0, kXLSpotSphere = 1, kXLMesh = 2, kXLSun = 3, kXLBg = 4;
 template <bool DIFF = false, int XL = kXLNone, int GL = kGLNone>
 __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, int li, const SurfPt& sp, v3 wo,
                                          unsigned pixelSample, unsigned soffs, unsigned loffs,
@@ -2172,6 +2195,9 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
   // outside the sample loops
   if (L.type == YK_LIGHT_AREA)
     return gen_sampled<DIFF, YK_LIGHT_AREA, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
+  if (XL >= kXLBg && L.type == YK_LIGHT_BACKGROUND)
+    return gen_sampled<DIFF, YK_LIGHT_BACKGROUND, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced,
+                                                      ml + L.mesh);
   if (XL >= kXLSun && L.type == YK_LIGHT_SUN)
     return gen_sampled<DIFF, YK_LIGHT_SUN, GL>(B, c, k0, L, M, sp, wo, pixelSample, soffs, loffs, traced);
   if (XL >= kXLMesh && L.type == YK_LIGHT_MESH)
@@ -2214,7 +2240,12 @@ __device__ __forceinline__ int gen_light(const Batch& B, long long c, int k0, in
 // (DLight::color holds it). A sun's rays are unbounded (t = -1) in both
 // halves; the split slot form marks a BSDF-half ray by the sign of its w, so
 // there the unbounded one is stored as -inf (unpack_shadow: tmax = +inf, which
-// the any-hit traversal takes as it takes a negative tmax). A sphere light's
+// the any-hit traversal takes as it takes a negative tmax). A background
+// light differs from the sun in one thing: ls.col / lcol is per sample, the
+// background evaluated at the sampled direction (illumSample) or at the
+// re-mapped BSDF direction (intersect); it takes lcol's place in the same
+// operand positions. Its slots have no aux form: transparent shadows are
+// refused on a scene that holds one (yk_render_shard). A sphere light's
 // canIntersect() is false (spherelight.cc:49): no MIS weight on its light
 // samples and no BSDF half, so it owns `samples` slots, not 2 * samples.
 template <bool DIFF, int KIND, int GL>
@@ -2225,7 +2256,7 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
   const c3 black = C3(0.f, 0.f, 0.f);
   const int n = L.samples;
   const unsigned offs = (unsigned)(n * (int)pixelSample) + soffs + loffs * 4567u;
-  const c3 lcol = C3(L.color[0], L.color[1], L.color[2]);
+  c3 lcol = C3(L.color[0], L.color[1], L.color[2]);  // YK_LIGHT_BACKGROUND: set per sample
   int nr = 0;
   Halton h2, h3;
   hal_start(h2, 2u, offs - 1u);
@@ -2242,6 +2273,10 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
     else if (KIND == YK_LIGHT_MESH) lit = mesh_illum(L, *ml, sp.P, s1, s2, ldir, ltmax, lpdf, tri);
     else if (KIND == YK_LIGHT_SPOT) lit = spot_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf, cv);
     else if (KIND == YK_LIGHT_SUN) lit = sun_illum(L, s1, s2, ldir, ltmax, lpdf);
+    else if (KIND == YK_LIGHT_BACKGROUND) {
+      float u, v;
+      lit = bg_illum(L, *ml, s1, s2, ldir, ltmax, lpdf, lcol, u, v);
+    }
     else lit = sphere_illum(L, sp.P, s1, s2, ldir, ltmax, lpdf);
     if (!lit) {
       put_slot(B, slot, 0, black);
@@ -2291,14 +2326,20 @@ __device__ __forceinline__ int gen_sampled(const Batch& B, long long c, int k0, 
       if (KIND == YK_LIGHT_AREA) hit = light_hit(L, sp.P, bdir, bt, lightPdf);
       else if (KIND == YK_LIGHT_MESH) hit = mesh_hit(L, *ml, sp.P, bdir, bt, lightPdf, tri);
       else if (KIND == YK_LIGHT_SUN) hit = sun_hit(L, bdir, bt, lightPdf);
+      else if (KIND == YK_LIGHT_BACKGROUND) {
+        float u, v;
+        bt = -1.f;  // the shadow ray's own tmax: intersect() leaves t alone
+        hit = bg_hit(L, *ml, bdir, lightPdf, lcol, u, v);
+      }
       else hit = spot_hit(L, sp.P, bdir, bt, lightPdf, cv);
     }
     if (!hit) {
       put_slot(B, slot, 0, black);
       continue;
     }
-    if (KIND == YK_LIGHT_SUN && B.split) bt = __uint_as_float(0x7f800000u);  // unbounded, as a MIS record holds it
-    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0; mesh: bt >= MIN_RAYDIST; sun: -1
+    if ((KIND == YK_LIGHT_SUN || KIND == YK_LIGHT_BACKGROUND) && B.split)
+      bt = __uint_as_float(0x7f800000u);  // unbounded, as a MIS record holds it
+    nr += emit_shadow<true>(B, slot, sp.P, bdir, bt, k0 + n + i, traced);  // area: bt > 1e-10; spot: bt >= 0; mesh: bt >= MIN_RAYDIST; sun, background: -1
     if (!(lightPdf > 1e-6f)) {
       put_slot(B, slot, SL_TRACED, black);
       continue;
@@ -2500,8 +2541,9 @@ __global__ void __launch_bounds__(YK_PRIMARY_BLOCK) k_shade_primary(DScene S, Ba
         }
       }
       alpha = 1.0f;
-    } else if (R.has_bg) {  // nothing hit: col += (*background)(ray), constant color
-      col = cadd(col, C3(R.bg[0], R.bg[1], R.bg[2]));
+    } else if (R.has_bg) {  // nothing hit: col += (*background)(ray)
+      const c3 bg = R.has_bg == kBgGradient ? bg_gradient(R.bg_grad, ld3(B.p_rays[c].dir)) : C3(R.bg[0], R.bg[1], R.bg[2]);
+      col = cadd(col, bg);
     }
     B.prim_hit[c] = ph;
     B.col[3 * c] = col.r;
@@ -2706,10 +2748,13 @@ __attribute__((amdgpu_waves_per_eu(DIFF ? YK_BOUNCE_WAVES_D : YK_BOUNCE_WAVES)))
       const long long c = B.q_owner[qin][qi];
       // background: "continue" at depth 1, "break" later; a caustic segment
       // adds the background first (pathtracer.cc:279-286)
-      if (R.spec && depth >= 2 && B.caus[c] && R.has_bg) {
-        B.pathcol[3 * c] = B.pathcol[3 * c] + B.thr[3 * c] * R.bg[0];
-        B.pathcol[3 * c + 1] = B.pathcol[3 * c + 1] + B.thr[3 * c + 1] * R.bg[1];
-        B.pathcol[3 * c + 2] = B.pathcol[3 * c + 2] + B.thr[3 * c + 2] * R.bg[2];
+      // (a scene of diffuse-only materials has no specular recursion and no caustic segment:
+      // its instantiation, the headline's, carries none of this)
+      if (!DIFF && R.spec && depth >= 2 && B.caus[c] && R.has_bg) {
+        const c3 bg = R.has_bg == kBgGradient ? bg_gradient(R.bg_grad, ld3(B.q_rays[qin][qi].dir)) : C3(R.bg[0], R.bg[1], R.bg[2]);
+        B.pathcol[3 * c] = B.pathcol[3 * c] + B.thr[3 * c] * bg.r;
+        B.pathcol[3 * c + 1] = B.pathcol[3 * c + 1] + B.thr[3 * c + 1] * bg.g;
+        B.pathcol[3 * c + 2] = B.pathcol[3 * c + 2] + B.thr[3 * c + 2] * bg.b;
       }
       B.pstate[c] = 0;
     }

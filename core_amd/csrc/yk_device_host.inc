@@ -38,10 +38,11 @@ constexpr TraceInfo kTrace[kTraceVariants] = {
 // kMatGlossy: a material is glossy (kGLGlossy); kMatCoated: one is coated glossy (kGLCoated);
 // kMatGlass: one is glass (kGLGlass, which holds the glossy and coated code too)
 enum ShadeMat { kMatDiffuse, kMatGeneral, kMatGlossy, kMatCoated, kMatGlass, kShadeMats };
-constexpr int kXLLevels = kXLSun + 1;
+constexpr int kXLLevels = kXLBg + 1;
 struct ShadeVariant {
   int mat = kMatGeneral;  // ShadeMat
-  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light; kXLSun: a sun
+  int xl = kXLNone;       // kXLSpotSphere: the scene holds a spot or sphere light; kXLMesh: a mesh light; kXLSun: a sun;
+                          // kXLBg: a background light
 };
 struct ShadeKernels {
   decltype(&k_shade_primary<false, kXLNone, false>) primary[2];  // [AO]
@@ -79,27 +80,31 @@ struct ShadeKernels {
 // estimateOneDirectLight may pick the sun) and k_photon_emit (emitPhoton)
 // have instantiations of their own; at every other level they are the
 // kernels they were before the sun.
+// A background light (kXLBg) sits above the sun: its two table searches and
+// the double acos of its sphere map reach k_shade_primary and k_shade_bounce
+// of such scenes alone. Photon maps refuse the light (yk_photon_build), so
+// k_fg_hit and k_photon_emit of this level are the sun level's.
 template <int MAT, int XL>
 constexpr ShadeKernels shade_cell() {
   constexpr bool DIFF = MAT == kMatDiffuse;
   constexpr int GL = MAT == kMatGlass ? kGLGlass : MAT == kMatCoated ? kGLCoated : (MAT == kMatGlossy ? kGLGlossy : kGLNone);
   return {{k_shade_primary<DIFF, XL, false, GL>, k_shade_primary<DIFF, XL, true, GL>}, k_shade_bounce<DIFF, XL, GL>,
           bounce_block(DIFF), k_path_start<DIFF, GL>, k_spawn<(GL >= kGLCoated ? GL : kGLNone)>,
-          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL, (XL == kXLSun ? kXLSun : kXLNone)>,
-          k_photon_emit<(XL == kXLSun ? kXLSun : kXLNone)>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>,
+          k_fg_start<DIFF, GL>, k_fg_hit<DIFF, GL, (XL >= kXLSun ? kXLSun : kXLNone)>,
+          k_photon_emit<(XL >= kXLSun ? kXLSun : kXLNone)>, k_pm_post<GL>, k_pm_finish<GL>, k_pt_caustic<GL>,
           k_photon_hit<GL>};
 }
 constexpr ShadeKernels kShade[kShadeMats][kXLLevels] = {
     {shade_cell<kMatDiffuse, kXLNone>(), shade_cell<kMatDiffuse, kXLSpotSphere>(), shade_cell<kMatDiffuse, kXLMesh>(),
-     shade_cell<kMatDiffuse, kXLSun>()},
+     shade_cell<kMatDiffuse, kXLSun>(), shade_cell<kMatDiffuse, kXLBg>()},
     {shade_cell<kMatGeneral, kXLNone>(), shade_cell<kMatGeneral, kXLSpotSphere>(), shade_cell<kMatGeneral, kXLMesh>(),
-     shade_cell<kMatGeneral, kXLSun>()},
+     shade_cell<kMatGeneral, kXLSun>(), shade_cell<kMatGeneral, kXLBg>()},
     {shade_cell<kMatGlossy, kXLNone>(), shade_cell<kMatGlossy, kXLSpotSphere>(), shade_cell<kMatGlossy, kXLMesh>(),
-     shade_cell<kMatGlossy, kXLSun>()},
+     shade_cell<kMatGlossy, kXLSun>(), shade_cell<kMatGlossy, kXLBg>()},
     {shade_cell<kMatCoated, kXLNone>(), shade_cell<kMatCoated, kXLSpotSphere>(), shade_cell<kMatCoated, kXLMesh>(),
-     shade_cell<kMatCoated, kXLSun>()},
+     shade_cell<kMatCoated, kXLSun>(), shade_cell<kMatCoated, kXLBg>()},
     {shade_cell<kMatGlass, kXLNone>(), shade_cell<kMatGlass, kXLSpotSphere>(), shade_cell<kMatGlass, kXLMesh>(),
-     shade_cell<kMatGlass, kXLSun>()},
+     shade_cell<kMatGlass, kXLSun>(), shade_cell<kMatGlass, kXLBg>()},
 };
 // below the sun's level the table names no instantiation beyond those it named before: no glossy k_spawn, no
 // DIFF or XL where a kernel takes none; the sun's level adds k_fg_hit and k_photon_emit of its own
@@ -113,6 +118,14 @@ static_assert(kShade[kMatGlossy][kXLNone].spawn == kShade[kMatGeneral][kXLNone].
               kShade[kMatCoated][kXLSun].fg_hit != kShade[kMatCoated][kXLNone].fg_hit &&
               kShade[kMatDiffuse][kXLSun].photon_emit != kShade[kMatDiffuse][kXLNone].photon_emit &&
               kShade[kMatDiffuse][kXLSun].path_start == kShade[kMatDiffuse][kXLNone].path_start);
+static_assert(kBgNone == YK_BG_NONE && kBgConstant == YK_BG_CONSTANT && kBgGradient == YK_BG_GRADIENT,
+              "the device's background kinds are the scene's");
+// the background light's level adds k_shade_primary and k_shade_bounce alone
+static_assert(kShade[kMatGeneral][kXLBg].bounce != kShade[kMatGeneral][kXLSun].bounce &&
+              kShade[kMatGeneral][kXLBg].primary[0] != kShade[kMatGeneral][kXLSun].primary[0] &&
+              kShade[kMatGlass][kXLBg].fg_hit == kShade[kMatGlass][kXLSun].fg_hit &&
+              kShade[kMatDiffuse][kXLBg].photon_emit == kShade[kMatDiffuse][kXLSun].photon_emit &&
+              kShade[kMatCoated][kXLBg].spawn == kShade[kMatCoated][kXLNone].spawn);
 // the glass row names kernels of its own wherever the coated row does, and the coated row names what it named before
 static_assert(kShade[kMatCoated][kXLNone].spawn == &k_spawn<kGLCoated> &&
               kShade[kMatCoated][kXLNone].bounce == &k_shade_bounce<false, kXLNone, kGLCoated> &&
@@ -169,8 +182,9 @@ struct yk_device {
   DBuf<yk_ray> nray;
   DBuf<unsigned> nsoffs, npsample;
   DBuf<unsigned long long> ncount, spec_words;
-  bool has_bg = false;
+  int bg_kind = kBgNone;  // the scene's background: kBgConstant (bg) or kBgGradient (bg_grad)
   float bg[3] = {0.f, 0.f, 0.f};
+  float bg_grad[12] = {};
   std::vector<DLight> lights_host;
   // photon maps of yk_photon_build (photonIntegrator_t::preprocess)
   bool pm_ready = false;
@@ -284,7 +298,8 @@ bool same_constants(const yk_device* a, const yk_device* b) {
           std::memcmp(a->mats_host.data(), b->mats_host.data(), a->mats_host.size() * sizeof(DMat)) == 0) &&
          (a->lights_host.empty() ||
           std::memcmp(a->lights_host.data(), b->lights_host.data(), a->lights_host.size() * sizeof(DLight)) == 0) &&
-         a->has_bg == b->has_bg && std::memcmp(a->bg, b->bg, sizeof a->bg) == 0;
+         a->bg_kind == b->bg_kind && std::memcmp(a->bg, b->bg, sizeof a->bg) == 0 &&
+         std::memcmp(a->bg_grad, b->bg_grad, sizeof a->bg_grad) == 0;
 }
 
 // the traversal watchdog fired (corrupt tree or stack): YK_ERR_INTERNAL

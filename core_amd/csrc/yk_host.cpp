@@ -488,14 +488,84 @@ int yk_scene_set_background(yk_scene* s, const float* rgb, float power) {
   if (!s) return set_error(YK_ERR_ARG, "yk_scene_set_background: NULL scene");
   s->s.has_background = rgb != nullptr;
   for (int k = 0; k < 3; ++k) s->s.background[k] = rgb ? rgb[k] * power : 0.f;  // col*power, textureback.cc:218
+  if (rgb) s->s.set_gradient_background(nullptr);  // one background per scene
+  if (s->s.has_bg_light()) s->s.built = false;     // the light's tables come from the background
   return YK_OK;
 }
 
 int yk_scene_get_background(const yk_scene* s, float* rgb_out, int32_t* has_out) {
   if (!s) return set_error(YK_ERR_ARG, "yk_scene_get_background: NULL scene");
+  if (s->s.has_gradient) return set_error(YK_ERR_STATE, "the scene's background is a gradient");
   if (rgb_out)
     for (int k = 0; k < 3; ++k) rgb_out[k] = s->s.background[k];
   if (has_out) *has_out = s->s.has_background ? 1 : 0;
+  return YK_OK;
+}
+
+int yk_scene_set_gradient_background(yk_scene* s, const yk_gradient_background* g) {
+  if (!s) return set_error(YK_ERR_ARG, "yk_scene_set_gradient_background: NULL scene");
+  if (g) {
+    bool finite = std::isfinite(g->power);
+    for (int k = 0; k < 3; ++k)
+      finite = finite && std::isfinite(g->horizon_color[k]) && std::isfinite(g->zenith_color[k]) &&
+               std::isfinite(g->horizon_ground_color[k]) && std::isfinite(g->zenith_ground_color[k]);
+    if (!finite) return set_error(YK_ERR_ARG, "gradient background needs finite colours and power");
+  }
+  s->s.set_gradient_background(g);
+  if (s->s.has_bg_light()) s->s.built = false;
+  return YK_OK;
+}
+
+int yk_scene_get_gradient_background(const yk_scene* s, yk_gradient_background* out, int32_t* has_out) {
+  if (!s) return set_error(YK_ERR_ARG, "yk_scene_get_gradient_background: NULL scene");
+  if (out && s->s.has_gradient) *out = s->s.gradient_params;
+  if (has_out) *has_out = s->s.has_gradient ? 1 : 0;
+  return YK_OK;
+}
+
+int yk_scene_add_background_light(yk_scene* s, const yk_background_light* l) {
+  if (!s || !l) return set_error(YK_ERR_ARG, "yk_scene_add_background_light: NULL argument");
+  if (l->samples < 1) return set_error(YK_ERR_ARG, "background light needs samples >= 1");
+  YK_GUARD_BEGIN
+  s->s.add_background_light(*l);
+  return YK_OK;
+  YK_GUARD_END
+}
+
+int yk_scene_get_background_light(const yk_scene* s, int32_t i, yk_background_light* out) {
+  if (!s || !out || i < 0 || i >= (int32_t)s->s.bg_lights.size())
+    return set_error(YK_ERR_ARG, "yk_scene_get_background_light: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_BACKGROUND) return set_error(YK_ERR_STATE, "light is not a background light");
+  *out = s->s.bg_lights[i].params;
+  return YK_OK;
+}
+
+int yk_scene_export_background_light(const yk_scene* s, int32_t i, int32_t* nrows_out, int32_t* total_u_out,
+                                     int32_t* row_count, int32_t* row_offset, float* row_integral,
+                                     float* row_inv_integral, float* func_u, float* cdf_u, float* func_v,
+                                     float* cdf_v, float* v_integrals) {
+  if (!s || i < 0 || i >= (int32_t)s->s.bg_lights.size())
+    return set_error(YK_ERR_ARG, "yk_scene_export_background_light: bad arguments");
+  if (s->s.light_kind[i] != YK_LIGHT_BACKGROUND) return set_error(YK_ERR_STATE, "light is not a background light");
+  if (!s->s.built) return set_error(YK_ERR_STATE, "yk_scene_export_background_light: scene not built");
+  const yk::BgLight& L = s->s.bg_lights[i];
+  auto copy = [](auto* dst, const auto& v) {
+    if (dst) std::memcpy(dst, v.data(), v.size() * sizeof v[0]);
+  };
+  if (nrows_out) *nrows_out = (int32_t)L.row_count.size();
+  if (total_u_out) *total_u_out = (int32_t)L.func_u.size();
+  copy(row_count, L.row_count);
+  copy(row_offset, L.row_offset);
+  copy(row_integral, L.row_integral);
+  copy(row_inv_integral, L.row_inv_integral);
+  copy(func_u, L.func_u);
+  copy(cdf_u, L.cdf_u);
+  copy(func_v, L.func_v);
+  copy(cdf_v, L.cdf_v);
+  if (v_integrals) {
+    v_integrals[0] = L.v_integral;
+    v_integrals[1] = L.v_inv_integral;
+  }
   return YK_OK;
 }
 
@@ -572,6 +642,8 @@ int yk_scene_build(yk_scene* s) {
     if (ntris > YK_MESH_LIGHT_MAX_TRIS)
       return set_error(YK_ERR_UNSUPPORTED, "mesh light has more than YK_MESH_LIGHT_MAX_TRIS triangles");
   }
+  if (s->s.has_bg_light() && s->s.background_kind() == yk::YK_BG_NONE)
+    return set_error(YK_ERR_STATE, "yk_scene_build: a background light needs a background");
   YK_GUARD_BEGIN
   s->s.finalize();
   return YK_OK;

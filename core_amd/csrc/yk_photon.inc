@@ -683,9 +683,10 @@ k_fg_hit(DScene S, Batch B, RenderConst R, PMConst PM,
     if (valid && prim < 0) {  // background: the path ends (a caustic segment adds the background first)
       const long long c = B.q_owner[qin][qi];
       if (it > 0 && (B.pstate[c] & FG_CAUS) && R.has_bg) {
-        B.pathcol[3 * c] = B.pathcol[3 * c] + B.thr[3 * c] * R.bg[0];
-        B.pathcol[3 * c + 1] = B.pathcol[3 * c + 1] + B.thr[3 * c + 1] * R.bg[1];
-        B.pathcol[3 * c + 2] = B.pathcol[3 * c + 2] + B.thr[3 * c + 2] * R.bg[2];
+        const c3 bg = R.has_bg == kBgGradient ? bg_gradient(R.bg_grad, ld3(B.q_rays[qin][qi].dir)) : C3(R.bg[0], R.bg[1], R.bg[2]);
+        B.pathcol[3 * c] = B.pathcol[3 * c] + B.thr[3 * c] * bg.r;
+        B.pathcol[3 * c + 1] = B.pathcol[3 * c + 1] + B.thr[3 * c + 1] * bg.g;
+        B.pathcol[3 * c + 2] = B.pathcol[3 * c + 2] + B.thr[3 * c + 2] * bg.b;
       }
       B.pstate[c] = 0;
     }

@@ -114,6 +114,11 @@ int yk_photon_build(yk_device* d, const yk_render_params* p, yk_photon_info* inf
       return set_error(YK_ERR_UNSUPPORTED,
                        "yk_photon_build: the scene holds a mesh light, whose photon emission is not supported "
                        "(direct lighting and path tracing without photon caustics are)");
+  for (const DLight& L : d->lights_host)  // bgLight_t::emitPhoton is not on the path
+    if (L.type == YK_LIGHT_BACKGROUND)
+      return set_error(YK_ERR_UNSUPPORTED,
+                       "yk_photon_build: the scene holds a background light, whose photon emission is not supported "
+                       "(direct lighting and path tracing without photon caustics are)");
   if (!pt && q.photons <= 0) return set_error(YK_ERR_ARG, "photons must be > 0");
   if (!pt && (q.search < 1 || q.search > kMaxSearch)) return set_error(YK_ERR_UNSUPPORTED, "search must be in [1, 256]");
   if (q.caustic_mix < 1 || q.caustic_mix > kMaxSearch) return set_error(YK_ERR_UNSUPPORTED, "caustic_mix must be in [1, 256]");

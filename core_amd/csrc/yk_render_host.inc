@@ -84,6 +84,9 @@ int check_render_params(const yk_device* d, const yk_render_params* p, int32_t s
   // ray in 9 registers, so at most 8 transparent surfaces (defaults 4-5)
   if (p->transp_shadows && (p->shadow_depth < 0 || p->shadow_depth > 8))
     return set_error(YK_ERR_UNSUPPORTED, "shadowDepth must be in [0, 8] with transpShad");
+  // a slot's aux record applies one light colour at resolve: none per sample
+  if (p->transp_shadows && d->shade.xl >= kXLBg)
+    return set_error(YK_ERR_UNSUPPORTED, "transparent shadows are not supported on a scene that holds a background light");
   if (ps.flags && (p->xstart + p->width > 65535 || p->ystart + p->height > 65535))
     return set_error(YK_ERR_UNSUPPORTED, "adaptive passes need coordinates < 65536");
   if (const int rc = check_depth_params(p)) return rc;
@@ -255,8 +258,9 @@ const char* build_frame_plan(const yk_device* d, const yk_render_params* p, int3
   R.integrator = p->integrator;
   R.transp_bg = p->transp_background;
   R.nlights = d->nlights;
-  R.has_bg = d->has_bg ? 1 : 0;
+  R.has_bg = d->bg_kind;
   for (int k = 0; k < 3; ++k) R.bg[k] = d->bg[k];
+  for (int k = 0; k < 12; ++k) R.bg_grad[k] = d->bg_grad[k];
   R.d1 = F.d1;
   R.spec = d->spec ? 1 : 0;
   R.trace_caustics =

@@ -50,10 +50,11 @@ __global__ void k_qmc_probe(int fn, const void* in, const uint32_t* in2, long lo
 }
 
 // yk_debug_light_probe: the shading kernels' own light functions (dirac_illum,
-// light_illum / spot_illum / sphere_illum / mesh_illum / sun_illum, light_hit /
-// spot_hit / sphere_hit / mesh_hit / sun_hit) on light li of the bound
-// constants (ml: the handle's mesh-light records); col as gen_light /
-// gen_sampled form it. EMIT_PHOTON: k_photon_emit's emit_photon.
+// light_illum / spot_illum / sphere_illum / mesh_illum / sun_illum / bg_illum,
+// light_hit / spot_hit / sphere_hit / mesh_hit / sun_hit / bg_hit) on light li
+// of the bound constants (ml: the handle's mesh-light records, which reach a
+// background light's tables too); col as gen_light / gen_sampled form it.
+// EMIT_PHOTON: k_photon_emit's emit_photon.
 __global__ void k_light_probe(int li, int fn, const float* in, long long n, float* out, const DMeshLight* ml) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -65,6 +66,34 @@ __global__ void k_light_probe(int li, int fn, const float* in, long long n, floa
   float tmax = 0.f, pdf = 0.f, cv = 1.f;
   int tri = 0;
   c3 col = C3(0.f, 0.f, 0.f);
+  if (L.type == YK_LIGHT_BACKGROUND) {  // per-sample colour, and the sampled or mapped (u, v) beside it
+    float u = 0.f, v = 0.f;
+    if (fn == YK_LIGHT_PROBE_ILLUM_SAMPLE) {
+      const float* x = in + 5 * i;
+      bg_illum(L, ml[L.mesh], x[3], x[4], dir, tmax, pdf, col, u, v);
+      o[0] = 1.f;
+      o[1] = dir.x;
+      o[2] = dir.y;
+      o[3] = dir.z;
+      o[4] = tmax;
+      o[5] = col.r;
+      o[6] = col.g;
+      o[7] = col.b;
+      o[8] = pdf;
+    } else if (fn == YK_LIGHT_PROBE_INTERSECT) {
+      bg_hit(L, ml[L.mesh], ld3(in + 6 * i + 3), pdf, col, u, v);
+      o[0] = 1.f;  // t and t_set stay 0: intersect() never writes t
+      o[3] = col.r;
+      o[4] = col.g;
+      o[5] = col.b;
+      o[6] = pdf;
+    } else {
+      return;  // illuminate() is false; emitPhoton is not on the path
+    }
+    o[YK_LIGHT_PROBE_U] = u;
+    o[YK_LIGHT_PROBE_V] = v;
+    return;
+  }
   if (fn == YK_LIGHT_PROBE_EMIT_PHOTON) {
     const float* x = in + 4 * i;
     if (L.type != YK_LIGHT_AREA && L.type != YK_LIGHT_POINT && L.type != YK_LIGHT_DIRECTIONAL && L.type != YK_LIGHT_SUN)

@@ -537,6 +537,51 @@ DLight make_mesh_light(const MeshLight& ML, int depth, MeshLightPack& P) {
   return D;
 }
 
+// bgLight_t as a DLight bound to the scene's background, with what init(scene)
+// takes from the scene bound (bglight.cc:112-117, as make_sun_light): aPdf =
+// worldRadius * worldRadius. Its tables go to the mesh-light pack as one run
+// of words in the order bg_tables reads them.
+DLight make_bg_light(const Scene& S, const BgLight& BL, MeshLightPack& P) {
+  const float* bound = S.tree.bound;
+  DLight D{};
+  D.type = YK_LIGHT_BACKGROUND;
+  D.soft = 1;  // light_sampled(): doLightEstimation's sample loops
+  D.samples = BL.params.samples;
+  D.nslots = 2 * BL.params.samples;  // table samples + BSDF (MIS) samples
+  D.bg.kind = S.background_kind();
+  D.bg.abs_inter = BL.params.abs_intersect ? 1 : 0;
+  D.bg.v_inv_integral = BL.v_inv_integral;
+  D.bg.total_u = (int)BL.func_u.size();
+  for (int k = 0; k < 12; ++k) D.bg.grad[k] = S.gradient[k];
+  for (int k = 0; k < 3; ++k) {
+    D.color[k] = S.background[k];
+    D.epos[k] = 0.5f * (bound[k] + bound[3 + k]);
+  }
+  const float dx = bound[3] - bound[0], dy = bound[4] - bound[1], dz = bound[5] - bound[2];
+  D.wradius = (float)(0.5 * (double)std::sqrt(dx * dx + dy * dy + dz * dz));
+  D.area = D.wradius * D.wradius;
+  D.mesh = (int)P.recs.size();
+  DMeshLight R{};  // nnodes == 0: no mesh behind it (upload_mesh_lights)
+  R.n = (int)BL.row_count.size();
+  P.recs.push_back(R);
+  P.off.push_back(P.f.size());
+  P.off.push_back(P.nodes.size() / 2);
+  P.off.push_back(P.leaf.size());
+  auto words = [&P](const std::vector<int32_t>& v) {
+    const size_t at = P.f.size();
+    P.f.resize(at + v.size());
+    std::memcpy(&P.f[at], v.data(), v.size() * sizeof(int32_t));
+  };
+  words(BL.row_count);
+  words(BL.row_offset);
+  P.f.insert(P.f.end(), BL.row_inv_integral.begin(), BL.row_inv_integral.end());
+  P.f.insert(P.f.end(), BL.func_v.begin(), BL.func_v.end());
+  P.f.insert(P.f.end(), BL.cdf_v.begin(), BL.cdf_v.end());
+  P.f.insert(P.f.end(), BL.func_u.begin(), BL.func_u.end());
+  P.f.insert(P.f.end(), BL.cdf_u.begin(), BL.cdf_u.end());
+  return D;
+}
+
 // The light records in scene order, and the mesh lights' arrays packed.
 std::vector<DLight> build_lights(const Scene& S, const std::vector<int>& mesh_depth, MeshLightPack& P) {
   std::vector<DLight> lights;
@@ -547,6 +592,7 @@ std::vector<DLight> build_lights(const Scene& S, const std::vector<int>& mesh_de
       case YK_LIGHT_SPOT: lights.push_back(make_spot_light(S.spot_states[i])); break;
       case YK_LIGHT_SPHERE: lights.push_back(make_sphere_light(S.sphere_states[i])); break;
       case YK_LIGHT_SUN: lights.push_back(make_sun_light(S.sun_states[i], S.tree.bound)); break;
+      case YK_LIGHT_BACKGROUND: lights.push_back(make_bg_light(S, S.bg_lights[i], P)); break;
       default:
         lights.push_back(make_dirac_light(S.dirac_states[i]));
         if (lights.back().type == YK_LIGHT_DIRECTIONAL) directional_photon_frame(lights.back(), S.tree.bound);
@@ -560,14 +606,15 @@ void upload_mesh_lights(yk_device* d, MeshLightPack& P) {
   d->S.ml = nullptr;
   if (P.recs.empty()) return;
   d->ml_f.ensure(P.f.size());
-  d->ml_nodes.ensure(P.nodes.size() / 2);
-  d->ml_leaf.ensure(P.leaf.size());
+  d->ml_nodes.ensure(std::max<size_t>(P.nodes.size() / 2, 1));
+  d->ml_leaf.ensure(std::max<size_t>(P.leaf.size(), 1));
   d->ml_recs.ensure(P.recs.size());
   for (size_t k = 0; k < P.recs.size(); ++k) {
     DMeshLight& R = P.recs[k];
     const size_t n = (size_t)R.n;
     const float* f = d->ml_f.p + P.off[3 * k];
     R.cdf = f;
+    if (R.nnodes == 0) continue;  // a background light's tables (make_bg_light): cdf alone
     R.verts = f + (n + 1);
     R.tris = R.verts + 9 * n;
     R.nrm = R.tris + kTriWords * n + kRecPad;
@@ -575,8 +622,10 @@ void upload_mesh_lights(yk_device* d, MeshLightPack& P) {
     R.leaf = d->ml_leaf.p + P.off[3 * k + 2];
   }
   HIPCHK(hipMemcpy(d->ml_f.p, P.f.data(), P.f.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d->ml_nodes.p, P.nodes.data(), P.nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d->ml_leaf.p, P.leaf.data(), P.leaf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!P.nodes.empty())
+    HIPCHK(hipMemcpy(d->ml_nodes.p, P.nodes.data(), P.nodes.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (!P.leaf.empty())
+    HIPCHK(hipMemcpy(d->ml_leaf.p, P.leaf.data(), P.leaf.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d->ml_recs.p, P.recs.data(), P.recs.size() * sizeof(DMeshLight), hipMemcpyHostToDevice));
   d->S.ml = d->ml_recs.p;
 }
@@ -585,7 +634,8 @@ void upload_mesh_lights(yk_device* d, MeshLightPack& P) {
 int light_level(const std::vector<DLight>& lights) {
   int xl = kXLNone;
   for (const DLight& L : lights)
-    xl = std::max(xl, L.type == YK_LIGHT_SUN    ? kXLSun
+    xl = std::max(xl, L.type == YK_LIGHT_BACKGROUND ? kXLBg
+                      : L.type == YK_LIGHT_SUN  ? kXLSun
                       : L.type == YK_LIGHT_MESH ? kXLMesh
                       : (L.type == YK_LIGHT_SPOT || L.type == YK_LIGHT_SPHERE) ? kXLSpotSphere : kXLNone);
   return xl;
@@ -713,8 +763,9 @@ int yk_device_upload(yk_device* d, const yk_scene* s) {
   d->lights_host = std::move(lights);
   d->mats_host = std::move(mats);
   d->pm_ready = false;
-  d->has_bg = S.has_background;
+  d->bg_kind = S.background_kind();
   for (int k = 0; k < 3; ++k) d->bg[k] = S.background[k];
+  for (int k = 0; k < 12; ++k) d->bg_grad[k] = S.gradient[k];
   d->cam_host = make_cam(S.camera_state);
   d->cam_resx = S.camera_state.resx;
   d->cam_resy = S.camera_state.resy;

@@ -178,7 +178,8 @@ class Scene:
         return st, cdf, areas
 
     def set_background(self, color, power=1.0):
-        """constant background (textureback.cc:206-218, ibl off); None removes it"""
+        """constant background (textureback.cc:206-218, ibl off), replacing a gradient one; None removes
+        the constant background and leaves a gradient alone (remove_gradient_background)"""
         if color is None:
             A.check(A.lib().yk_scene_set_background(self._p, None, 0.0))
         else:
@@ -186,10 +187,56 @@ class Scene:
             A.check(A.lib().yk_scene_set_background(self._p, rgb, power))
 
     def background(self):
+        """the constant background's colour (times power), or None; YkError(YK_ERR_STATE) under a gradient"""
         rgb = (C.c_float * 3)()
         has = C.c_int32()
         A.check(A.lib().yk_scene_get_background(self._p, rgb, C.byref(has)))
         return tuple(rgb) if has.value else None
+
+    def set_gradient_background(self, horizon_color=(1, 1, 1), zenith_color=(0.4, 0.5, 1), horizon_ground_color=None,
+                                zenith_ground_color=None, power=1.0):
+        """gradientback (gradientback.cc:81-97) with the factory's defaults: the ground colours default
+        to the sky's; replaces a constant background"""
+        g = A.yk_gradient_background(A.f3(*horizon_color), A.f3(*zenith_color),
+                                     A.f3(*(horizon_color if horizon_ground_color is None else horizon_ground_color)),
+                                     A.f3(*(zenith_color if zenith_ground_color is None else zenith_ground_color)),
+                                     power)
+        A.check(A.lib().yk_scene_set_gradient_background(self._p, C.byref(g)))
+
+    def remove_gradient_background(self):
+        A.check(A.lib().yk_scene_set_gradient_background(self._p, None))
+
+    def gradient_background(self):
+        """yk_gradient_background as set, or None"""
+        g = A.yk_gradient_background()
+        has = C.c_int32()
+        A.check(A.lib().yk_scene_get_gradient_background(self._p, C.byref(g), C.byref(has)))
+        return g if has.value else None
+
+    def add_background_light(self, samples=16, shoot_caustics=True, shoot_diffuse=True, abs_intersect=False):
+        """bglight (bglight.cc:277-292; what "ibl" of a background creates): the scene's background as a
+        light, appended to the light list; bound to the background at build()"""
+        l = A.yk_background_light(samples, int(shoot_caustics), int(shoot_diffuse), int(abs_intersect))
+        A.check(A.lib().yk_scene_add_background_light(self._p, C.byref(l)))
+
+    def background_light_tables(self, i):
+        """bgLight_t's tables of light i after build(): a dict of row_count, row_offset, row_integral,
+        row_inv_integral, func_u, cdf_u, func_v, cdf_v (numpy arrays) and v_integral, v_inv_integral"""
+        L = A.lib()
+        nrows, total = C.c_int32(), C.c_int32()
+        none = (None,) * 9
+        A.check(L.yk_scene_export_background_light(self._p, i, C.byref(nrows), C.byref(total), *none))
+        nv, nu = nrows.value, total.value
+        t = dict(row_count=np.zeros(nv, np.int32), row_offset=np.zeros(nv, np.int32),
+                 row_integral=np.zeros(nv, np.float32), row_inv_integral=np.zeros(nv, np.float32),
+                 func_u=np.zeros(nu, np.float32), cdf_u=np.zeros(nu + nv, np.float32),
+                 func_v=np.zeros(nv, np.float32), cdf_v=np.zeros(nv + 1, np.float32))
+        vi = np.zeros(2, np.float32)
+        ptr = [t[k].ctypes.data_as(A.i32p if t[k].dtype == np.int32 else A.fp) for k in
+               ("row_count", "row_offset", "row_integral", "row_inv_integral", "func_u", "cdf_u", "func_v", "cdf_v")]
+        A.check(L.yk_scene_export_background_light(self._p, i, None, None, *ptr, vi.ctypes.data_as(A.fp)))
+        t["v_integral"], t["v_inv_integral"] = vi[0], vi[1]
+        return t
 
     def set_camera(self, from_, to, up, resx, resy, focal=1.0, aspect_ratio=1.0, near_clip=0.0,
                    far_clip=-1.0, aperture=0.0, dof_distance=0.0, bokeh_type=0, bokeh_bias=0, bokeh_rotation=0.0,
@@ -255,14 +302,15 @@ class Scene:
 
     def light_states(self):
         """Per light: yk_area_light_state, yk_dirac_light_state, yk_spot_light_state,
-        yk_sphere_light_state, yk_sun_light_state or yk_mesh_light_state (each getter answers YK_ERR_STATE for
-        the other kinds; a mesh light's state needs a built scene)."""
+        yk_sphere_light_state, yk_sun_light_state, yk_background_light or yk_mesh_light_state (each getter
+        answers YK_ERR_STATE for the other kinds; a mesh light's state needs a built scene)."""
         L = A.lib()
         getters = ((A.yk_area_light_state, L.yk_scene_get_area_light_state),
                    (A.yk_dirac_light_state, L.yk_scene_get_dirac_light_state),
                    (A.yk_spot_light_state, L.yk_scene_get_spot_light_state),
                    (A.yk_sphere_light_state, L.yk_scene_get_sphere_light_state),
                    (A.yk_sun_light_state, L.yk_scene_get_sun_light_state),
+                   (A.yk_background_light, L.yk_scene_get_background_light),
                    (A.yk_mesh_light_state, lambda p, k, m: L.yk_scene_get_mesh_light_state(p, k, m, None, None, 0)))
         out = []
         for k in range(self.info().nlights):

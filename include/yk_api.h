@@ -110,9 +110,11 @@ enum { YK_BRDF_LAMBERT = 0, YK_BRDF_OREN_NAYAR = 1 };
 /* YK_LIGHT_MESH is the kind yk_scene_get_light and the device state report for
  * a mesh light; it is added with yk_scene_add_mesh_light, and
  * yk_scene_add_light answers YK_ERR_UNSUPPORTED for it (yk_light has no room
- * for object ids). */
+ * for object ids). YK_LIGHT_BACKGROUND (bgLight_t) likewise has an entry point
+ * of its own, yk_scene_add_background_light: yk_scene_add_light answers
+ * YK_ERR_UNSUPPORTED for it and yk_scene_get_light YK_ERR_STATE. */
 enum { YK_LIGHT_AREA = 0, YK_LIGHT_POINT = 1, YK_LIGHT_DIRECTIONAL = 2, YK_LIGHT_SPOT = 3, YK_LIGHT_SPHERE = 4,
-       YK_LIGHT_MESH = 5, YK_LIGHT_SUN = 6 };
+       YK_LIGHT_MESH = 5, YK_LIGHT_SUN = 6, YK_LIGHT_BACKGROUND = 7 };
 typedef struct yk_light {
   int32_t type;
   /* area: areaLight_t::factory, arealight.cc:171-192 */
@@ -645,10 +647,77 @@ int yk_scene_get_sphere_light_state(const yk_scene* s, int32_t i, yk_sphere_ligh
 int yk_scene_add_sun_light_state(yk_scene* s, const yk_sun_light_state* l);
 int yk_scene_get_sun_light_state(const yk_scene* s, int32_t i, yk_sun_light_state* out);
 /* constBackground_t (textureback.cc:187-218, "constant", ibl off): camera
- * rays that miss add color*power. rgb NULL removes the background. */
+ * rays that miss add color*power. Setting it replaces a gradient background.
+ * rgb NULL removes the constant background and leaves a gradient one alone
+ * (yk_scene_set_gradient_background with NULL removes that). */
 int yk_scene_set_background(yk_scene* s, const float* rgb, float power);
-/* has_out = 0 when the scene has no background */
+/* has_out = 0 when the scene has no background. YK_ERR_STATE when the scene's
+ * background is a gradient (yk_scene_get_gradient_background reads that). */
 int yk_scene_get_background(const yk_scene* s, float* rgb_out, int32_t* has_out);
+/* gradientBackground_t (gradientback.cc:60-97, "gradientback"): a ray that
+ * misses adds eval(dir): blend = dir.z; blend >= 0: blend * zenith +
+ * (1.f - blend) * horizon, else the ground pair with -blend; a colour whose
+ * smallest channel is below 1e-6f becomes (1e-5f, 1e-5f, 1e-5f). The four
+ * colours are multiplied by power when set, as the factory does. It is a miss
+ * colour wherever the constant background is one (camera rays, specular
+ * recursion nodes, caustic segments), under all three integrators. Setting
+ * either background replaces the other; g NULL removes a gradient (and leaves
+ * a constant background alone). YK_ERR_ARG for a non-finite colour or power.
+ * On a scene that holds a background light, setting or removing a background
+ * returns the scene to the unbuilt state: the light's tables are made from
+ * the background by yk_scene_build.
+ * "sunsky", "darksky" and "textureback" backgrounds and bgPortalLight are not
+ * on the GPU path. */
+typedef struct yk_gradient_background {
+  float horizon_color[3];        /* "horizon_color" [1,1,1]                */
+  float zenith_color[3];         /* "zenith_color" [0.4,0.5,1]             */
+  float horizon_ground_color[3]; /* "horizon_ground_color" [= horizon]     */
+  float zenith_ground_color[3];  /* "zenith_ground_color" [= zenith]       */
+  float power;                   /* "power" [1]                            */
+} yk_gradient_background;
+int yk_scene_set_gradient_background(yk_scene* s, const yk_gradient_background* g);
+/* has_out = 0 (and out untouched) when the scene's background is not a
+ * gradient; otherwise out holds the colours and power as they were set */
+int yk_scene_get_gradient_background(const yk_scene* s, yk_gradient_background* out, int32_t* has_out);
+/* bgLight_t (bglight.cc, "bglight"; what "ibl" of the constant and gradient
+ * backgrounds creates): the scene's background as a sampled light with
+ * `samples` importance samples over its tables and as many BSDF (MIS) samples
+ * per estimate (canIntersect() is true), all unbounded rays; ls.col / lcol is
+ * the background evaluated per sample. The light is appended to the light
+ * list at the call and binds to whichever background the scene has at
+ * yk_scene_build, which builds its tables (bgLight_t::init, bglight.cc:68-118:
+ * 360 rows of 16..720 columns, one pdf1D_t per row and one over the rows'
+ * integrals) and answers YK_ERR_STATE when the scene has no background.
+ * YK_ERR_ARG unless samples >= 1.
+ * Not on the GPU path, refused and never approximated:
+ *  - emitPhoton: yk_photon_build answers YK_ERR_UNSUPPORTED ("background
+ *    light") on a scene that holds one -- photon mapping, caustic_type photon
+ *    / both and dl_caustics alike, so YK_INTEGRATOR_PHOTON cannot render it;
+ *  - transparent shadows: a render with transp_shadows != 0 is
+ *    YK_ERR_UNSUPPORTED (the slot's aux record applies one light colour at
+ *    resolve and has no room for a per-sample one). */
+typedef struct yk_background_light {
+  int32_t samples;        /* "samples" / "ibl_samples" [16]                               */
+  int32_t shoot_caustics; /* [1 gradient, 0 constant]; photon-only, held, not used here   */
+  int32_t shoot_diffuse;  /* [1]; likewise                                                */
+  int32_t abs_intersect;  /* "abs_intersect" [0]: intersect() negates the direction       */
+} yk_background_light;
+int yk_scene_add_background_light(yk_scene* s, const yk_background_light* l);
+/* YK_ERR_STATE when light i is of another kind */
+int yk_scene_get_background_light(const yk_scene* s, int32_t i, yk_background_light* out);
+/* The tables of background light i of a built scene, bit for bit; any pointer
+ * may be NULL. nrows_out: vDist->count (360). Per row y: row_count[y] =
+ * uDist[y]->count, row_offset[y] = the row's first element in func_u (its cdf
+ * starts at cdf_u[row_offset[y] + y], since a cdf holds count + 1 entries),
+ * row_integral[y] / row_inv_integral[y] = uDist[y]->integral / invIntegral.
+ * func_u holds sum(row_count) floats, cdf_u sum(row_count) + nrows; func_v
+ * nrows (= the rows' integrals), cdf_v nrows + 1; v_integrals[2] =
+ * {vDist->integral, vDist->invIntegral}. total_u_out = sum(row_count), so a
+ * first call with NULL arrays sizes the second. invCount is 1.f / count. */
+int yk_scene_export_background_light(const yk_scene* s, int32_t i, int32_t* nrows_out, int32_t* total_u_out,
+                                     int32_t* row_count, int32_t* row_offset, float* row_integral,
+                                     float* row_inv_integral, float* func_u, float* cdf_u, float* func_v,
+                                     float* cdf_v, float* v_integrals);
 int yk_scene_set_camera_state(yk_scene* s, const yk_camera_state* c);
 int yk_scene_get_material_state(const yk_scene* s, int32_t i, yk_material_state* out);
 int yk_scene_get_area_light_state(const yk_scene* s, int32_t i, yk_area_light_state* out);
